@@ -35,6 +35,17 @@ no data-path collective (weak scaling); after the timed region the per-trajector
 costs are all-gathered once (the fit result exchange) and that time is reported
 separately.
 
+A plain run (`--gpus N --steps K --warmup W`) does only that: set-up, settle, warm-up,
+the K timed steps, the result line with the headline's fields. `--dump-outputs DIR`
+also writes what the last timed fit returned (x, u, cost, iters, status of `ilqr_fit`,
+rank 0's) as DIR/<name>.npy in float64, a fixed seeded sample of the trajectories when
+the whole would pass 64 MB; the instances are seeded, so two builds run with the same
+arguments are comparable output for output. `--full` adds every other section of the
+line, each measured after the timed region in runs of its own: the kernel legs and
+rooflines, the one-iteration step, the co-headline and default-options fits, the
+line-search replay and its checks, the result all-gather of a multi-rank run, the
+secondary configurations (`--no-secondary` skips them) and the CPU baseline (`--no-cpu`).
+
 Prints ONE JSON line (rank 0).
 """
 from __future__ import annotations
@@ -252,11 +263,33 @@ def reduce_over_ranks(times, dflt_iters, world, device):
     if world == 1:
         return dict(times), dflt_iters
     import torch.distributed as tdist
-    t = torch.tensor([times[k] for k in RANK_TIMES], dtype=torch.float64, device=device)
+    keys = [k for k in RANK_TIMES if k in times]   # a plain run has ms_step alone
+    t = torch.tensor([times[k] for k in keys], dtype=torch.float64, device=device)
     tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
     it = torch.tensor([dflt_iters], dtype=torch.float64, device=device)
     tdist.all_reduce(it, op=tdist.ReduceOp.SUM)
-    return dict(zip(RANK_TIMES, t.tolist())), float(it.item()) / world
+    return dict(zip(keys, t.tolist())), float(it.item()) / world
+
+
+DUMP_LIMIT_BYTES = 64e6
+
+
+def dump_outputs(path, out, seed=0):
+    """`--dump-outputs`: the last timed fit's results (`out`: name -> host array, batch
+    first) as path/<name>.npy in float64. When they would pass DUMP_LIMIT_BYTES together,
+    the same seeded sample of trajectories is kept of each (its indices: sample_index.npy)."""
+    batch = len(out["cost"])
+    per_traj = 8 * (1 + sum(int(np.prod(a.shape[1:])) for a in out.values()))
+    idx = None
+    if batch * per_traj > DUMP_LIMIT_BYTES:
+        keep = int(DUMP_LIMIT_BYTES // per_traj)
+        idx = np.sort(np.random.default_rng(seed).choice(batch, keep, replace=False))
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        kept = a if idx is None else a[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(kept, dtype=np.float64))
+    if idx is not None:
+        np.save(os.path.join(path, "sample_index.npy"), idx.astype(np.float64))
 
 
 def aggregate_fields(tm, dflt_iters, world):
@@ -350,11 +383,15 @@ def main():
                     help="seconds of untimed fits before warmup (the GPU clock settles after ~0.1-0.5 s of load)")
     ap.add_argument("--batch", type=int, default=4096, help="trajectories per GPU")
     ap.add_argument("--T", type=int, default=100)
-    ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds for the CPU baseline sample")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline (module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed fit's x, u, cost, iters, status as DIR/<name>.npy")
+    ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds for the CPU baseline sample (--full)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--forward", default="dpp", choices=["dpp", "mfma"],
                     help="the ring forward's mat-vecs: DPP row broadcasts or the 4-block f64 MFMA")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the configs 2 and 5 lines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the configs 2 and 5 lines")
     ap.add_argument("--dist-selftest", action="store_true",
                     help="multi-rank plumbing only, no GPU (gloo; tests/test_dist.py)")
     args = ap.parse_args()
@@ -362,6 +399,8 @@ def main():
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))  # no GPU call has been made in this process
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.dist_selftest:
         return dist_selftest(args, world, int(os.environ.get("RANK", "0")))
     rank = int(os.environ.get("RANK", "0"))
@@ -403,15 +442,16 @@ def main():
     fcost = torch.empty((B,), dtype=torch.float64, device=dev)
     fiters = torch.empty((B,), dtype=torch.int32, device=dev)
     fst = torch.empty((B,), dtype=torch.int32, device=dev)
-    xn, un = torch.empty_like(x), torch.empty_like(u)
-    pc = torch.empty((B,), dtype=torch.float64, device=dev)
-    st = torch.zeros((B,), dtype=torch.int32, device=dev)
-    trials = torch.empty((B,), dtype=torch.int32, device=dev)
-    d = torch.empty((B, T, NU), dtype=torch.float64, device=dev)
-    K = torch.empty((B, T, NU, NX), dtype=torch.float64, device=dev)
-    pinf = torch.full((B,), float("inf"), dtype=torch.float64, device=dev)
-    fwx, fwu = torch.empty_like(x), torch.empty_like(u)
-    fwc = torch.empty((B,), dtype=torch.float64, device=dev)
+    if args.full:  # the sections after the timed region
+        xn, un = torch.empty_like(x), torch.empty_like(u)
+        pc = torch.empty((B,), dtype=torch.float64, device=dev)
+        st = torch.zeros((B,), dtype=torch.int32, device=dev)
+        trials = torch.empty((B,), dtype=torch.int32, device=dev)
+        d = torch.empty((B, T, NU), dtype=torch.float64, device=dev)
+        K = torch.empty((B, T, NU, NX), dtype=torch.float64, device=dev)
+        pinf = torch.full((B,), float("inf"), dtype=torch.float64, device=dev)
+        fwx, fwu = torch.empty_like(x), torch.empty_like(u)
+        fwc = torch.empty((B,), dtype=torch.float64, device=dev)
     torch.cuda.synchronize()
 
     prob = s._p()
@@ -465,6 +505,59 @@ def main():
         fit_stats = {"fits": len(full), "median_ms_per_iteration": float(np.median(full)),
                      "p10_ms": float(np.percentile(full, 10)), "p90_ms": float(np.percentile(full, 90)),
                      "median_fit_ms": float(np.median(full)) * FIT_ITERS}
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # device copies, taken now: the sections of --full reuse the fit's result buffers
+        dumped = {"x": xo.clone(), "u": uo.clone(), "cost": fcost.clone(), "iters": fiters.clone(),
+                  "status": fst.clone()}
+    cnt = algorithmic_counts(T)
+    it_bytes = (cnt["bw_bytes"] + cnt["fw_bytes"]) * B
+    it_flops = (cnt["bw_flops"] + cnt["fw_flops"]) * B
+
+    def headline_result(ms_step):  # the fields of every run's line; ms_step: max over ranks
+        return {
+            "metric": "batched iLQR iterations/sec (fwd+bwd pass), nx=12 nu=4 T=100, 1/2/4/8 MI355X",
+            "value": world * 1000.0 / ms_step,
+            "unit": "batched iterations/s (one batched iteration = 4096 trajectories per GPU, backward+forward "
+                    f"with line search, inside a {FIT_ITERS}-iteration fit from cold)",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": ms_step,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic: per-instance randomised hover-linearised quadrotor LQ (SURVEY.md §8d)",
+            "config": {"workload": f"quadrotor-style LQ iLQR.fit, {FIT_ITERS} iterations from cold, tol disabled",
+                       "nx": NX, "nu": NU, "T": T, "batch_per_gpu": B, "global_batch": B * world,
+                       "parallelism": f"independent trajectories, {world} rank(s), no data-path collective",
+                       "forward": args.forward},
+            "full": args.full,
+            "clock_settle_s": settle_s, "clock_settle_fits": n_settle,
+            "fit_timing": fit_stats,
+            "fit_calls_ok": not fit_rc,
+            "iteration": {"traj_iters_per_s": world * B * 1000.0 / ms_step,
+                          "algorithmic_bytes": it_bytes, "algorithmic_flops": it_flops,
+                          "hbm_gbps": it_bytes / (ms_step * 1e-3) / 1e9,
+                          "hbm_frac": it_bytes / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                          "fp64_tflops": it_flops / (ms_step * 1e-3) / 1e12,
+                          "event_ms": ms, "wall_ms": ms_wall},
+        }
+
+    def write_dump():
+        if dumped is not None:
+            dump_outputs(args.dump_outputs, {n: t.cpu().numpy() for n, t in dumped.items()})
+
+    if not args.full:  # a plain run ends here
+        tm, _ = reduce_over_ranks({"ms_step": ms_step}, 0.0, world, dev if backend == "nccl" else "cpu")
+        write_dump()
+        if rank == 0:
+            print(json.dumps(headline_result(tm["ms_step"])), flush=True)
+        s.close()
+        if dist:
+            tdist.destroy_process_group()
+        return
 
     # secondary: the round-1 step (one iteration from cold per step, ilqr_iterate)
     opts1 = _lib.default_options(tol=-1.0)
@@ -619,12 +712,9 @@ def main():
     if world == 1 and not args.no_secondary:
         secondary = secondary_configs(local)
 
-    cnt = algorithmic_counts(T)
     bw_flops = cnt["bw_flops"] * B
     bw_bytes = cnt["bw_bytes"] * B
     fw_bytes = cnt["fw_bytes"] * B
-    it_bytes = (cnt["bw_bytes"] + cnt["fw_bytes"]) * B
-    it_flops = (cnt["bw_flops"] + cnt["fw_flops"]) * B
     pmc, pmc_src = load_pmc_traffic(os.path.join(ROOT, "profiles"), B, T)
     traffic = pmc["hbm_bytes_per_backward_launch"] if pmc else None
     fused_traffic = pmc["hbm_bytes_per_fused_launch"] if pmc else None
@@ -635,26 +725,12 @@ def main():
     bw_floor_us = bw_flops / (FP64_PEAK_TFLOPS * 1e12) * 1e6
     fw_floor_us = fw_bytes / (HBM_COPY_GBPS * 1e9) * 1e6
 
-    result = {
-        "metric": "batched iLQR iterations/sec (fwd+bwd pass), nx=12 nu=4 T=100, 1/2/4/8 MI355X",
-        "value": agg["value"],
-        "unit": "batched iterations/s (one batched iteration = 4096 trajectories per GPU, backward+forward "
-                f"with line search, inside a {FIT_ITERS}-iteration fit from cold)",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_step,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic: per-instance randomised hover-linearised quadrotor LQ (SURVEY.md §8d)",
-        "config": {"workload": f"quadrotor-style LQ iLQR.fit, {FIT_ITERS} iterations from cold, tol disabled",
-                   "nx": NX, "nu": NU, "T": T, "batch_per_gpu": B, "global_batch": B * world,
-                   "parallelism": f"independent trajectories, {world} rank(s), no data-path collective",
-                   "forward": args.forward},
-        "clock_settle_s": settle_s, "clock_settle_fits": n_settle,
-        "fit_timing": fit_stats,
+    result = headline_result(ms_step)
+    result["iteration"].update({"mean_line_search_trials": float(np.mean(trials_per_iter[:FIT_ITERS])),
+                                "line_search_trials_per_iteration": trials_per_iter[:FIT_ITERS],
+                                "cost_strictly_decreasing": monotone, "all_ok": ok,
+                                "fit_equals_replay": fit_matches_replay})
+    result.update({
         # the kernel the timed region spends ≈97 % of its time in (one launch per fit
         # iteration): algorithmic flops and bytes of one batched iteration ÷
         # its mean launch time inside the fit chain; FP64-issue-bound, HBM beside it
@@ -687,16 +763,6 @@ def main():
         "serial_ceiling": {"backward_us_at_fp64_peak": bw_floor_us, "forward_us_at_copy_rate": fw_floor_us,
                            "batched_it_per_s": 1e6 / (bw_floor_us + fw_floor_us),
                            "note": "backward then forward, serialised per trajectory; 10k it/s needs overlap"},
-        "iteration": {"traj_iters_per_s": world * B * 1000.0 / ms_step,
-                      "algorithmic_bytes": it_bytes, "algorithmic_flops": it_flops,
-                      "hbm_gbps": it_bytes / (ms_step * 1e-3) / 1e9,
-                      "hbm_frac": it_bytes / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                      "fp64_tflops": it_flops / (ms_step * 1e-3) / 1e12,
-                      "mean_line_search_trials": float(np.mean(trials_per_iter[:FIT_ITERS])),
-                      "line_search_trials_per_iteration": trials_per_iter[:FIT_ITERS],
-                      "cost_strictly_decreasing": monotone, "all_ok": ok,
-                      "fit_equals_replay": fit_matches_replay,
-                      "event_ms": ms, "wall_ms": ms_wall},
         "fit_5_iterations": {"ms_per_iteration": fit5_ms / 5, "batched_it_per_s": agg["fit5_batched_it_per_s"],
                              "line_search_trials_per_iteration": trials_per_iter, "call_status": fit5_rc,
                              "trajectory_status_counts": fit5_status,
@@ -731,7 +797,8 @@ def main():
         "rank0_times": rank_times,
         "allgather_check": gathered,
         "cpu_baseline": None,
-    }
+    })
+    write_dump()
     if rank == 0 and world == 1 and not args.no_cpu:  # the CPU baseline: rank 0 at N = 1 only
         try:
             result["cpu_baseline"] = cpu_baseline(lq, x0, u0, args.cpu_budget)

@@ -3,8 +3,8 @@ profiles/mfma_<tag>.json (north_star: MFMA utilisation against the gfx950 peak).
 
 Run on the GPU box (one pass, no trace domains):
   rocprofv3 --pmc MfmaUtil MfmaFlopsF64 SQ_INSTS_VALU_MFMA_F64 SQ_INSTS_VALU GRBM_GUI_ACTIVE \
-      --kernel-trace --output-format csv -d gpurun_out/pmc_mfma -o run -- python bench.py --steps 5 --warmup 1 --no-cpu
-  python profiles/collect_mfma.py gpurun_out/pmc_mfma profiles/mfma_r02.json
+      --kernel-trace --output-format csv -d OUT/pmc_mfma -o run -- python bench.py --full --steps 5 --warmup 1 --no-cpu
+  python profiles/collect_mfma.py OUT/pmc_mfma profiles/mfma_r02.json
 
 MfmaUtil = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE · SIMDs) in %, MfmaFlopsF64 =
 SQ_INSTS_VALU_MFMA_MOPS_F64 · 512 (rocprofv3's derived counters). Per-dispatch values
@@ -42,7 +42,7 @@ def main(d, out):
             if k:
                 dur[k].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-9)
     res = {"source": "rocprofv3 --pmc MfmaUtil MfmaFlopsF64 SQ_INSTS_VALU_MFMA_F64 SQ_INSTS_VALU GRBM_GUI_ACTIVE, "
-                     "python bench.py --steps 5 --warmup 1 --no-cpu", "peak_fp64_tflops": 78.6}
+                     "python bench.py --full --steps 5 --warmup 1 --no-cpu", "peak_fp64_tflops": 78.6}
     for k, cs in vals.items():
         e = {c: sum(v) / len(v) for c, v in cs.items()}
         if dur.get(k):

@@ -2,9 +2,9 @@
 for the backward / forward kernels of bench.py into profiles/pmc_<tag>.json.
 
 Run on the GPU box (see tools/gpu_round.sh `pmc`):
-  rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -o run -- python bench.py --steps 5 --warmup 1 --no-cpu
-  rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write -o run -- python bench.py --steps 5 --warmup 1 --no-cpu
-  python profiles/collect_pmc.py gpurun_out/pmc_fetch gpurun_out/pmc_write profiles/pmc_r01.json
+  rocprofv3 --pmc FETCH_SIZE --output-format csv -d OUT/pmc_fetch -o run -- python bench.py --full --steps 5 --warmup 1 --no-cpu
+  rocprofv3 --pmc WRITE_SIZE --output-format csv -d OUT/pmc_write -o run -- python bench.py --full --steps 5 --warmup 1 --no-cpu
+  python profiles/collect_pmc.py OUT/pmc_fetch OUT/pmc_write profiles/pmc_r01.json
 
 Units: FETCH_SIZE / WRITE_SIZE are KiB per dispatch. Correction per
 MI355X_MICROARCH.md §HBM: on gfx950 FETCH_SIZE reads exactly half the bytes of
@@ -40,7 +40,7 @@ def main(fetch_dir, write_dir, out):
     fetch = read(fetch_dir, "FETCH_SIZE")
     write = read(write_dir, "WRITE_SIZE")
     res = {"batch": 4096, "T": 100, "units": "bytes per launch",
-           "source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, python bench.py"}
+           "source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, python bench.py --full"}
     for k in sorted(set(fetch) | set(write)):
         f = fetch.get(k, 0.0) * 1024
         w = write.get(k, 0.0) * 1024

@@ -54,6 +54,32 @@ def test_loader_orders_rounds_numerically_and_ignores_other_benches(tmp_path):
     assert rec is None and "pmc_r10.json" in src and "batch=8192" in src
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: float64 files of the whole result under the size limit; above it the
+    same seeded sample of trajectories of every array, identical from call to call."""
+    import numpy as np
+    rng = np.random.default_rng(1)
+    out = {"x": rng.standard_normal((50, 5, 3)), "u": rng.standard_normal((50, 4, 2)),
+           "cost": rng.standard_normal(50), "iters": np.full(50, 3, np.int32), "status": np.arange(50, dtype=np.int32)}
+    bench.dump_outputs(str(tmp_path / "a"), out)
+    assert sorted(os.listdir(tmp_path / "a")) == ["cost.npy", "iters.npy", "status.npy", "u.npy", "x.npy"]
+    for k, v in out.items():
+        got = np.load(tmp_path / "a" / (k + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, v)
+    per_traj = 8 * (1 + 15 + 8 + 3)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 20.5 * per_traj)
+    bench.dump_outputs(str(tmp_path / "b"), out)
+    bench.dump_outputs(str(tmp_path / "c"), out)
+    idx = np.load(tmp_path / "b" / "sample_index.npy").astype(int)
+    assert len(idx) == 20 and len(set(idx)) == 20 and (np.diff(idx) > 0).all()
+    total = 0
+    for k, v in out.items():
+        got = np.load(tmp_path / "b" / (k + ".npy"))
+        assert np.array_equal(got, v[idx]) and np.array_equal(got, np.load(tmp_path / "c" / (k + ".npy")))
+        total += got.nbytes
+    assert total + idx.size * 8 <= bench.DUMP_LIMIT_BYTES
+
+
 def test_malformed_headline_record_fails_loudly(tmp_path):
     d = tmp_path / "profiles"
     d.mkdir()

@@ -26,7 +26,7 @@ from oracle import dual
 from oracle import rbd as RBD
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-REF_URDF = "/root/reference/test/urdf"
+REF_URDF = os.path.join(GOLD, "urdf")  # the reference's test/urdf descriptions, stored as fixtures
 
 
 @pytest.fixture(scope="module")
@@ -120,7 +120,6 @@ def test_reference_costs_restated():
     assert fcost(x) == pytest.approx(1e5 * (10 * 0.5 ** 2 + 10 * 0.2 ** 2))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_URDF), reason="reference URDFs only in the build container")
 @pytest.mark.parametrize("name", ["2Dof_arm", "6Dof_arm"])
 def test_shipped_robots_match_the_reference_urdfs(name):
     a, b = parse_urdf(os.path.join(REF_URDF, name + ".urdf")), load_robot(name.lower())

@@ -180,7 +180,7 @@ def test_bench_two_ranks_gloo(gpu):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["ILQR_DIST_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--steps", "6",
                         "--warmup", "3", "--settle", "0.1", "--batch", "512", "--no-cpu", "--no-secondary"],
                        env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -190,3 +190,42 @@ def test_bench_two_ranks_gloo(gpu):
     assert out["n_gpus"] == 2 and out["config"]["global_batch"] == 1024
     assert out["allgather_check"]["trajectories"] == 1024 and out["allgather_check"]["finite_costs"] == 1024
     assert out["value"] > 0 and out["iteration"]["all_ok"]
+
+
+def test_bench_plain_run_dumps_last_timed_fit(gpu, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` prints the headline's fields alone;
+    `--dump-outputs` holds what its last timed fit returned: K = 4 steps are one 3-iteration
+    fit and one of 1 iteration, whose result is Solver.fit's for the same seeded instances,
+    bit for bit."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+                        "--settle", "0.1", "--batch", "300", "--T", "20", "--dump-outputs", str(tmp_path / "out")],
+                       env=env, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 4 and out["fit_timing"]["fits"] == 1 and out["fit_calls_ok"] and not out["full"]
+    assert out["ms_per_step"] > 0 and out["value"] == pytest.approx(1000.0 / out["ms_per_step"])
+    assert out["higher_is_better"] and out["dtype"] == "f64" and out["unit"].startswith("batched iterations/s")
+    for section in ("roofline", "co_headline", "cpu_baseline", "secondary_configs", "fit_default_options"):
+        assert section not in out
+    lq, x, u = quadrotor_batch(300, T=20, seed0=0)
+    s = Solver(12, 4, 20, 300)
+    s.set_problem(lq)
+    s.set_schedule(forward_mfma=False)  # the bench's call
+    try:
+        f = s.fit(torch.from_numpy(x).cuda(), torch.from_numpy(u).cuda(), max_iter=1, tol=-1.0)
+        want = {"x": f.x, "u": f.u, "cost": f.cost, "iters": f.iters, "status": f.status}
+        for name, t in want.items():
+            got = np.load(tmp_path / "out" / (name + ".npy"))
+            assert got.dtype == np.float64
+            np.testing.assert_array_equal(got, t.cpu().numpy().astype(np.float64), err_msg=name)
+    finally:
+        s.close()
+    assert sorted(os.listdir(tmp_path / "out")) == ["cost.npy", "iters.npy", "status.npy", "u.npy", "x.npy"]

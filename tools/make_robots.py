@@ -1,6 +1,6 @@
-"""Parse the reference's URDFs (test/urdf/*.urdf) into the chain descriptions the
-RBD family loads at run time (ilqr.jl_amd/ilqr_amd/robots/*.json): the GPU box has
-no /root/reference. Run here: python tools/make_robots.py"""
+"""Parse the reference's URDFs (test/urdf/*.urdf, stored under tests/golden/urdf) into
+the chain descriptions the RBD family loads at run time
+(ilqr.jl_amd/ilqr_amd/robots/*.json). Run: python tools/make_robots.py"""
 import json
 import os
 import sys
@@ -9,7 +9,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "ilqr.jl_amd")]
 from ilqr_amd.urdf import parse_urdf  # noqa: E402
 
-SRC = "/root/reference/test/urdf"
+SRC = os.path.join(ROOT, "tests", "golden", "urdf")
 OUT = os.path.join(ROOT, "ilqr.jl_amd", "ilqr_amd", "robots")
 for name in ("2Dof_arm", "6Dof_arm"):
     ch = parse_urdf(os.path.join(SRC, name + ".urdf"))
