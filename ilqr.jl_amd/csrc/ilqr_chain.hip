@@ -20,7 +20,9 @@
 //    wave on the 4-block f64 MFMA for 2-joint chains, lane per trajectory otherwise)
 //    and the RK4 rollout + α-halving line search (a 16-lane group per trajectory,
 //    component-parallel Newton-Euler for chains of ≤ 3 joints), in the handle's dtype
-//    (fp32 or fp64).
+//    (fp32 or fp64). Six joints (the 6-DoF arm, fp64): the linearisation and the costs
+//    written as tiles for the wide tiles recursion (ilqr_tiles.hip) and a 32-lane
+//    forward group per trajectory — "Six-joint chains" below.
 // Layout as the other families (include/ilqr.h): x (B, T+1, nx), u/d (B, T, nu),
 // K (B, T, nu, nx), trajectory slowest, nx = 2·n_joints.
 #include <hip/hip_runtime.h>
@@ -555,6 +557,137 @@ __device__ __forceinline__ void chain_xdot_cv(const ChainK<V, NJ>& P, const V (&
     xd[i] = x[NJ + i];
     xd[NJ + i] = q2[i];
   }
+}
+
+// lane l ^ 16 of a 32-lane group (the other DPP row of the group): ds_swizzle in bit
+// mode, and 0x1F, or 0, xor 0x10 — a crossbar move, no LDS memory
+__device__ __forceinline__ double swap_rows(double x) {
+  const u2v p = __builtin_bit_cast(u2v, x);
+  const u2v q = {(unsigned)__builtin_amdgcn_ds_swizzle((int)p.x, 0x401F),
+                 (unsigned)__builtin_amdgcn_ds_swizzle((int)p.y, 0x401F)};
+  return __builtin_bit_cast(double, q);
+}
+
+// chain_xdot over a 32-lane group (six joints: seven passes do not fit the four roles of
+// a 16-lane group): eight quads, lane 4·role + c as in rnea_cv — role 0 the bias, roles
+// 1..NJ the columns of M, the rest idle passes (q̇ = q̈ = g = 0). The group is two DPP rows.
+//  * sin/cos: lane n of EACH row evaluates joint min(n, NJ − 1), and row_newbcast:i hands
+//    joint i's pair to the row — one polynomial pair per lane, no cross-row traffic;
+//  * b and M: the rows swap their τ once (swap_rows); after it both rows hold the even
+//    row's τ (roles 0..3: b and columns 0..2) and the odd row's (roles 4..6: columns 3..5)
+//    and row_newbcast picks lane 4·(role mod 4) of either.
+// Every lane then eliminates the same 6×6 system in the scalar pass's order.
+template <int NJ, int NU>
+__device__ __forceinline__ void chain_xdot_cv32(const ChainK<double, NJ>& P, const double (&x)[2 * NJ],
+                                                const double (&u)[NU], double (&xd)[2 * NJ]) {
+  using V = double;
+  static_assert(NJ + 1 <= 8 && NJ > 3, "one role per pass in a group of 32");
+  // the evaluation re-reads the chain constants from LDS: kept in registers across the
+  // four RK4 stages (≈160 lane-dependent doubles) they spill
+  asm volatile("" ::: "memory");
+  const int l32 = threadIdx.x & 31;
+  const int role = l32 >> 2, cmp = l32 & 3, n16 = l32 & 15;
+  const bool odd = (l32 & 16) != 0;
+  V c[NJ], s[NJ], qd[NJ], qdd[NJ], tau[NJ];
+  V ang = x[0];
+#pragma unroll
+  for (int i = 1; i < NJ; ++i) {
+    // an opaque copy: a select between two elements of x is otherwise folded into a load
+    // at a selected address, and x stays an array in scratch for it
+    V xi = x[i];
+    asm volatile("" : "+v"(xi));
+    if (n16 >= i) ang = xi;
+  }
+  // fast_sincos with the large-argument fallback in line: a call here (big_sincos) hands
+  // its results back through scratch and the live registers around it through spills
+  V so, co;
+  if (__builtin_expect(fabs(ang) > 1e5, 0)) sincos(ang, &so, &co);
+  else sincos_reduced(ang, so, co);
+  auto rowlane = [](V v, int n) {  // lane n of the row (n a constant after unrolling)
+    switch (n) {
+      case 0: return qperm<QP_ROWBC + 0>(v);
+      case 1: return qperm<QP_ROWBC + 1>(v);
+      case 2: return qperm<QP_ROWBC + 2>(v);
+      case 3: return qperm<QP_ROWBC + 3>(v);
+      case 4: return qperm<QP_ROWBC + 4>(v);
+      case 5: return qperm<QP_ROWBC + 5>(v);
+      case 6: return qperm<QP_ROWBC + 6>(v);
+      case 8: return qperm<QP_ROWBC + 8>(v);
+      default: return qperm<QP_ROWBC + 12>(v);
+    }
+  };
+#pragma unroll
+  for (int i = 0; i < NJ; ++i) {
+    s[i] = rowlane(so, i);
+    c[i] = rowlane(co, i);
+    qd[i] = role == 0 ? x[NJ + i] : V(0);
+    qdd[i] = V(role == i + 1 ? 1 : 0);
+  }
+  rnea_cv<true, true>(P, c, s, qd, qdd, tau, V(role == 0 ? 1 : 0), cmp);
+  V b[NJ], M[NJ][NJ];
+#pragma unroll
+  for (int i = 0; i < NJ; ++i) {
+    const V other = swap_rows(tau[i]);
+    const V ev = odd ? other : tau[i], od = odd ? tau[i] : other;
+    b[i] = rowlane(ev, 0);
+#pragma unroll
+    for (int k = 0; k < NJ; ++k) M[i][k] = rowlane(k + 1 < 4 ? ev : od, 4 * ((k + 1) & 3));
+  }
+  V r[NJ];
+#pragma unroll
+  for (int i = 0; i < NJ; ++i) r[i] = (i < NU ? u[i < NU ? i : 0] : V(0)) - b[i];
+#pragma unroll
+  for (int k = 0; k < NJ; ++k) {
+    const V inv = crecip(M[k][k]);
+#pragma unroll
+    for (int i = k + 1; i < NJ; ++i) {
+      const V lk = M[i][k] * inv;
+#pragma unroll
+      for (int j = k + 1; j < NJ; ++j) M[i][j] = M[i][j] - lk * M[k][j];
+      r[i] = r[i] - lk * r[k];
+    }
+  }
+  V q2[NJ];
+#pragma unroll
+  for (int i = NJ - 1; i >= 0; --i) {
+    V acc = r[i];
+#pragma unroll
+    for (int j = i + 1; j < NJ; ++j) acc = acc - M[i][j] * q2[j];
+    q2[i] = acc * crecip(M[i][i]);
+  }
+#pragma unroll
+  for (int i = 0; i < NJ; ++i) {
+    xd[i] = x[NJ + i];
+    xd[NJ + i] = q2[i];
+  }
+}
+
+// RK4 (chain_rk4's arithmetic and association: x + ⅙(((k₁ + 2k₂) + 2k₃) + k₄)) on the
+// 32-lane evaluation, the four stages as a loop: one evaluation is ≈1,900 instructions,
+// and unrolled the step neither fits the registers (the scheduler interleaves the stages'
+// DPP moves and constant reads) nor sits well in the instruction cache.
+template <int NJ, int NU>
+__device__ __forceinline__ void chain_rk4_cv32(const ChainK<double, NJ>& P, const double (&x)[2 * NJ],
+                                               const double (&u)[NU], double (&out)[2 * NJ]) {
+  constexpr int NX = 2 * NJ;
+  double y[NX], acc[NX];
+#pragma unroll
+  for (int i = 0; i < NX; ++i) y[i] = x[i];
+#pragma nounroll
+  for (int st = 0; st < 4; ++st) {
+    double k[NX];
+    chain_xdot_cv32<NJ, NU>(P, y, u, k);
+    const double wy = st == 2 ? 1.0 : 0.5;             // x + ½k₁, x + ½k₂, x + k₃
+    const double wa = (st == 0 || st == 3) ? 1.0 : 2.0;
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      k[i] = P.dt * k[i];
+      acc[i] = st == 0 ? k[i] : acc[i] + wa * k[i];
+      y[i] = x[i] + wy * k[i];
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NX; ++i) out[i] = x[i] + (1.0 / 6.0) * acc[i];
 }
 
 // ---------------------------------------------------------------------------
@@ -1901,6 +2034,367 @@ __global__ void chain_fit_init_kernel(int B, V* prev_cost, int32_t* status, int3
   iters[b] = 0;
 }
 
+// ---------------------------------------------------------------------------
+// Six-joint chains (the 6-DoF arm, nx = 12, nu = 6, fp64). The Riccati recursion is the
+// wide tiles kernel (launch_tiles_backward, ilqr_tiles.hip), so the linearisation and the
+// costs are written as the tiles it reads — A (B,T,12,12), B (B,T,12,6), lx, lu, lxx, luu,
+// lfx, lfxx — and the forward runs a 32-lane group per trajectory (chain_xdot_cv32).
+// ---------------------------------------------------------------------------
+// chain_linearize_kernel's lane map (one lane per (b, t, direction)) and arithmetic; lane
+// kd stores column kd of A_t (kd < NX) or column kd − NX of B_t
+constexpr int CHAIN6_FD_WAVES = 1, CHAIN6_DUAL_WAVES = 1;
+template <int NJ, int NU, int LIN>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LIN == ILQR_LINEARIZE_CENTRAL_FD ? CHAIN6_FD_WAVES : CHAIN6_DUAL_WAVES))) void chain_linearize_tiles_kernel(ChainK<double, NJ> P, int B, int T,
+                                                                    const double* __restrict__ x,
+                                                                    const double* __restrict__ u,
+                                                                    const int32_t* __restrict__ status,
+                                                                    double* __restrict__ A,
+                                                                    double* __restrict__ Bm) {
+  using V = double;
+  constexpr int NX = 2 * NJ, ND = NX + NU;
+  const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (size_t)B * T * ND) return;
+  const size_t bt = g / ND;
+  const int kd = (int)(g - bt * ND);
+  const int b = (int)(bt / T), t = (int)(bt - (size_t)b * T);
+  if (status && status[b] != ILQR_TRAJ_OK) return;
+  const V* xb = x + ((size_t)b * (T + 1) + t) * NX;
+  const V* ub = u + bt * NU;
+  V z[ND], col[NX];
+#pragma unroll
+  for (int k = 0; k < NX; ++k) z[k] = xb[k];
+#pragma unroll
+  for (int k = 0; k < NU; ++k) z[NX + k] = ub[k];
+  if constexpr (LIN == ILQR_LINEARIZE_DUAL) {
+    using D = DualT<1, V>;
+    D xs[NX], us[NU], o[NX];
+#pragma unroll
+    for (int k = 0; k < ND; ++k) {
+      D v(z[k]);
+      v.d[0] = (k == kd) ? V(1) : V(0);
+      if (k < NX) xs[k] = v; else us[k - NX] = v;
+    }
+    chain_rk4<NJ, NU>(P, xs, us, o);
+#pragma unroll
+    for (int i = 0; i < NX; ++i) col[i] = o[i].d[0];
+  } else {
+    // central differences, step h = ε^(1/3)·max(1, |z_k|), divided by the step actually taken
+    const V cbe = V(6.0554544523933395e-6);
+    V zk = z[0];
+#pragma unroll
+    for (int j = 1; j < ND; ++j)
+      if (j == kd) zk = z[j];
+    const V h = cbe * fmax(V(1), fabs(zk));
+    const V zp = zk + h, zm = zk - h;
+    V xp[NX], up[NU], xm[NX], um[NU], fp[NX], fm[NX];
+#pragma unroll
+    for (int j = 0; j < NX; ++j) {
+      xp[j] = j == kd ? zp : z[j];
+      xm[j] = j == kd ? zm : z[j];
+    }
+#pragma unroll
+    for (int j = 0; j < NU; ++j) {
+      up[j] = NX + j == kd ? zp : z[NX + j];
+      um[j] = NX + j == kd ? zm : z[NX + j];
+    }
+    chain_rk4<NJ, NU>(P, xp, up, fp);
+    chain_rk4<NJ, NU>(P, xm, um, fm);
+    const V inv = V(1) / (zp - zm);
+#pragma unroll
+    for (int i = 0; i < NX; ++i) col[i] = (fp[i] - fm[i]) * inv;
+  }
+  V* out = kd < NX ? A + bt * NX * NX + kd : Bm + bt * NX * NU + (kd - NX);
+  const int ld = kd < NX ? NX : NU;
+#pragma unroll
+  for (int i = 0; i < NX; ++i) out[i * ld] = col[i];
+}
+
+// the joint-space cost (RBD_helper_functions.jl:85-116) of an NJ-joint chain
+template <int NJ>
+struct ChainCostK {
+  double tgt[NJ], qw[NJ], rw[NJ], qfw[NJ];
+};
+
+// The cost tiles that change with (x, u), exactly as chain_backward_lane forms them
+// (immediate_cost_quadratization :81-109, final_cost_quadratization :134-153):
+// lx = −2qw(θ* − θ) on the joint rows, lu = 2rw·u, lfx = −2qfw(θ* − θ_N).
+// One lane per element: (b, t ≤ T, e < NX + NU), t = T the terminal row.
+template <int NJ, int NU>
+__global__ __launch_bounds__(256) void chain_cost_tiles_kernel(ChainCostK<NJ> C, int B, int T,
+                                                               const double* __restrict__ x,
+                                                               const double* __restrict__ u,
+                                                               const int32_t* __restrict__ status,
+                                                               double* __restrict__ lx, double* __restrict__ lu,
+                                                               double* __restrict__ lfx) {
+  constexpr int NX = 2 * NJ, NE = NX + NU;
+  const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (size_t)B * (T + 1) * NE) return;
+  const size_t bt = g / NE;
+  const int e = (int)(g - bt * NE);
+  const int b = (int)(bt / (T + 1)), t = (int)(bt - (size_t)b * (T + 1));
+  if (status && status[b] != ILQR_TRAJ_OK) return;
+  const int j = e < NJ ? e : (e >= NX ? e - NX : 0);  // the joint / input of this element
+  double tgt = C.tgt[0], qw = C.qw[0], rw = C.rw[0], qfw = C.qfw[0];
+#pragma unroll
+  for (int i = 1; i < NJ; ++i)
+    if (i == j) { tgt = C.tgt[i]; qw = C.qw[i]; rw = C.rw[i]; qfw = C.qfw[i]; }
+  if (e < NX) {
+    const double xe = x[((size_t)b * (T + 1) + t) * NX + e];
+    if (t == T) lfx[(size_t)b * NX + e] = e < NJ ? -2.0 * qfw * (tgt - xe) : 0.0;
+    else lx[((size_t)b * T + t) * NX + e] = e < NJ ? -2.0 * qw * (tgt - xe) : 0.0;
+  } else if (t < T) {
+    const size_t i = ((size_t)b * T + t) * NU + (e - NX);
+    lu[i] = 2.0 * rw * u[i];
+  }
+}
+
+// The Hessian tiles lxx = diag(2qw, 0), luu = diag(2rw), lfxx = diag(2qfw, 0): they depend
+// on neither the state nor the step, and the handle's cost is fixed, so they are written
+// once when the handle is created. One lane per (b, t ≤ T, element of the larger tile).
+template <int NJ, int NU>
+__global__ __launch_bounds__(256) void chain_cost_hessians_kernel(ChainCostK<NJ> C, int B, int T,
+                                                                  double* __restrict__ lxx,
+                                                                  double* __restrict__ luu,
+                                                                  double* __restrict__ lfxx) {
+  constexpr int NX = 2 * NJ;
+  const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (size_t)B * (T + 1) * NX * NX) return;
+  const size_t bt = g / (NX * NX);
+  const int e = (int)(g - bt * (NX * NX));
+  const int b = (int)(bt / (T + 1)), t = (int)(bt - (size_t)b * (T + 1));
+  const int r = e / NX, c = e - r * NX;
+  double qw = 0.0, rw = 0.0, qfw = 0.0;
+#pragma unroll
+  for (int i = 0; i < NJ; ++i)
+    if (i == r) { qw = C.qw[i]; qfw = C.qfw[i]; }
+  const int ru = e / NU, cu = e - ru * NU;
+#pragma unroll
+  for (int i = 0; i < NU; ++i)
+    if (i == ru) rw = C.rw[i];
+  if (t == T) {
+    lfxx[(size_t)b * NX * NX + e] = (r == c && r < NJ) ? 2.0 * qfw : 0.0;
+  } else {
+    const size_t s = (size_t)b * T + t;
+    lxx[s * NX * NX + e] = (r == c && r < NJ) ? 2.0 * qw : 0.0;
+    if (e < NU * NU) luu[s * NU * NU + e] = ru == cu ? 2.0 * rw : 0.0;
+  }
+}
+
+// Forward rollout + α-halving line search of a six-joint chain: chain_forward_lane's
+// arithmetic in its order, every lane of a 32-lane group carrying the same x̄, ū, cost and
+// Σδu² (the dynamics split over the group: chain_xdot_cv32).
+//  * Step inputs (K_t 6×12, x_t, x_traj_t's joint rows, u_t, δu_t: 102 doubles) are loaded
+//    one step ahead, lane l the words l, l + 32, … of the step's record, and handed to
+//    the group through LDS at the top of the step (as 72 + 30 registers per lane and
+//    step in flight they would not fit);
+//  * x̄_t and ū_t are stored by lanes 0..11 and 12..17 (one coalesced store each).
+constexpr int CH6_LANES = 32;
+constexpr int CH6_STAGE = 128;  // doubles per group: 4 words per lane
+template <int NJ, int NU>
+__device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P, double* __restrict__ stage,
+                                                     int b, int T, const double* __restrict__ x,
+                                                     const double* __restrict__ u,
+                                                     const double* __restrict__ xtraj,
+                                                     const double* __restrict__ dg,
+                                                     const double* __restrict__ Kg, double prev_cost,
+                                                     double* __restrict__ xnew, double* __restrict__ unew,
+                                                     double* du2_out, const LSParams& ls) {
+  using V = double;
+  constexpr int NX = 2 * NJ, NK = NU * NX;
+  constexpr int O_X = NK, O_XT = O_X + NX, O_U = O_XT + NJ, O_D = O_U + NU, N_IN = O_D + NU;
+  static_assert(N_IN <= CH6_STAGE && NX + NU <= CH6_LANES, "a step's inputs in four words per lane");
+  const int l32 = threadIdx.x & (CH6_LANES - 1);
+  const V* xb0 = x + (size_t)b * (T + 1) * NX;
+  const V* ub0 = u + (size_t)b * T * NU;
+  const V* xt0 = (xtraj ? xtraj : x) + (size_t)b * (T + 1) * NX;
+  const V xtw = xtraj ? V(1) : V(0);  // x_traj = NULL means zeros (forward_pass.jl:151)
+  const V* d0 = dg + (size_t)b * T * NU;
+  const V* K0 = Kg + (size_t)b * T * NK;
+  V* xo = xnew + (size_t)b * (T + 1) * NX;
+  V* uo = unew + (size_t)b * T * NU;
+  // this lane's four words of a step's record: source and stride per step (a word past the
+  // record re-reads K's first word and lands in the stage's unused tail)
+  const V* src[4];
+  int str[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int e = l32 + CH6_LANES * k;
+    src[k] = K0, str[k] = 0;
+    if (e < O_X) { src[k] = K0 + e; str[k] = NK; }
+    else if (e < O_XT) { src[k] = xb0 + (e - O_X); str[k] = NX; }
+    else if (e < O_U) { src[k] = xt0 + (e - O_XT); str[k] = NX; }
+    else if (e < O_D) { src[k] = ub0 + (e - O_U); str[k] = NU; }
+    else if (e < N_IN) { src[k] = d0 + (e - O_D); str[k] = NU; }
+  }
+  V alpha = V(ls.alpha0);
+  ChainFwdOut<V> out{V(0), 0, 0};
+  V du2 = V(0);
+  for (int trial = 1; trial <= ls.max_trials; ++trial) {
+    V xb[NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) xb[i] = xb0[i];  // x̄₁ = x₁ (:65)
+    V cost = V(0);
+    du2 = V(0);
+    V in[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) in[k] = src[k][0];
+    for (int t = 0; t < T; ++t) {
+      wave_lds_fence();  // the previous step's reads are done
+#pragma unroll
+      for (int k = 0; k < 4; ++k) stage[l32 + CH6_LANES * k] = in[k];
+      wave_lds_fence();
+      {
+        const size_t tn = t + 1 < T ? t + 1 : t;  // step t + 1's words, in flight during step t
+#pragma unroll
+        for (int k = 0; k < 4; ++k) in[k] = src[k][tn * str[k]];
+      }
+      V dx[NX];
+#pragma unroll
+      for (int i = 0; i < NX; ++i) dx[i] = xb[i] - stage[O_X + i];  // δx (:72)
+      V ubar[NU];
+#pragma unroll
+      for (int a = 0; a < NU; ++a) {  // ūₖ = uₖ + α δuₖ + Kₖ δx (:73)
+        V kdx = V(0);
+#pragma unroll
+        for (int i = 0; i < NX; ++i) kdx = fma(stage[a * NX + i], dx[i], kdx);
+        const V uk = stage[O_U + a];
+        ubar[a] = fma(alpha, stage[O_D + a], uk) + kdx;
+        const V e = ubar[a] - uk;
+        du2 = fma(e, e, du2);
+      }
+      // ℓ(x̄ₖ − x_trajₖ, ūₖ) (:187-190; RBD_helper_functions.jl:85-99 on the joints)
+      V lk = V(0);
+#pragma unroll
+      for (int i = 0; i < NJ; ++i) {
+        const V e = P.tgt[i] - fma(-xtw, stage[O_XT + i], xb[i]);
+        lk = fma(P.qw[i] * e, e, lk);
+      }
+#pragma unroll
+      for (int a = 0; a < NU; ++a) lk = fma(P.rw[a] * ubar[a], ubar[a], lk);
+      cost += lk;
+      {
+        V w = xb[0];
+#pragma unroll
+        for (int i = 1; i < NX; ++i)
+          if (l32 == i) w = xb[i];
+#pragma unroll
+        for (int a = 0; a < NU; ++a)
+          if (l32 == NX + a) w = ubar[a];
+        if (l32 < NX) xo[(size_t)t * NX + l32] = w;
+        else if (l32 < NX + NU) uo[(size_t)t * NU + (l32 - NX)] = w;
+      }
+      V xn[NX];
+      chain_rk4_cv32<NJ, NU>(P, xb, ubar, xn);  // x̄ₖ₊₁ = f(x̄ₖ, ūₖ) (:74)
+#pragma unroll
+      for (int i = 0; i < NX; ++i) xb[i] = xn[i];
+    }
+    {
+      V w = xb[0];
+#pragma unroll
+      for (int i = 1; i < NX; ++i)
+        if (l32 == i) w = xb[i];
+      if (l32 < NX) xo[(size_t)T * NX + l32] = w;
+    }
+    // final_cost(x̄_N) on the raw state (:192; RBD_helper_functions.jl:105-116)
+    V lf = V(0);
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) {
+      const V e = P.tgt[i] - xb[i];
+      lf = fma(P.qfw[i] * e, e, lf);
+    }
+    cost += lf;
+    out.trials = trial;
+    out.cost = cost;
+    if (prev_cost - cost > V(0)) {  // (:77-80); NaN compares false → keep searching
+      out.accepted = 1;
+      break;
+    }
+    alpha *= V(ls.shrink);  // (:82)
+  }
+  if (du2_out) *du2_out = du2;
+  return out;
+}
+
+constexpr int CH6_WG = 64;  // two trajectories per workgroup (one wave)
+
+template <int NJ>
+__device__ __forceinline__ void chain_consts_to_lds(ChainK<double, NJ>& Ps, const ChainK<double, NJ>& P) {
+  static_assert(sizeof(ChainK<double, NJ>) % 4 == 0, "dword copy");
+  for (int i = threadIdx.x; i < (int)(sizeof(ChainK<double, NJ>) / 4); i += CH6_WG)
+    reinterpret_cast<uint32_t*>(&Ps)[i] = reinterpret_cast<const uint32_t*>(&P)[i];
+  __syncthreads();
+}
+
+template <int NJ, int NU>
+__global__ __launch_bounds__(CH6_WG) void chain_forward32_kernel(
+    ChainK<double, NJ> P, int B, int T, const double* __restrict__ x, const double* __restrict__ u,
+    const double* __restrict__ xtraj, const double* __restrict__ d, const double* __restrict__ K,
+    const double* __restrict__ prev_cost, double* __restrict__ xnew, double* __restrict__ unew,
+    double* __restrict__ new_cost, int32_t* __restrict__ trials, int32_t* __restrict__ status, LSParams ls) {
+  constexpr int NX = 2 * NJ;
+  __shared__ ChainK<double, NJ> Ps;  // constants in LDS (see chain_iter_forward_kernel)
+  __shared__ double stage[(CH6_WG / CH6_LANES) * CH6_STAGE];
+  chain_consts_to_lds(Ps, P);
+  const int b = (blockIdx.x * CH6_WG + threadIdx.x) / CH6_LANES;
+  if (b >= B) return;  // the whole lane group
+  const int l32 = threadIdx.x & (CH6_LANES - 1);
+  const double pc = prev_cost ? prev_cost[b] : (double)INFINITY;
+  const ChainFwdOut<double> r = chain_forward_group32<NJ, NU>(
+      Ps, stage + (threadIdx.x / CH6_LANES) * CH6_STAGE, b, T, x, u, xtraj, d, K, pc, xnew, unew, nullptr, ls);
+  if (!r.accepted) {  // exhausted (the reference would loop forever): return the inputs
+    for (int i = l32; i < (T + 1) * NX; i += CH6_LANES)
+      xnew[(size_t)b * (T + 1) * NX + i] = x[(size_t)b * (T + 1) * NX + i];
+    for (int i = l32; i < T * NU; i += CH6_LANES) unew[(size_t)b * T * NU + i] = u[(size_t)b * T * NU + i];
+  }
+  if (l32 != 0) return;
+  new_cost[b] = r.cost;
+  if (trials) trials[b] = r.trials;
+  if (status) status[b] = r.accepted ? ILQR_TRAJ_OK
+                                     : (r.cost != r.cost ? ILQR_TRAJ_NAN : ILQR_TRAJ_LS_EXHAUSTED);
+}
+
+// fit iteration, forward part. bstatus is the tiles kernel's per-trajectory result of this
+// iteration's backward pass (it runs every trajectory): a NaN gain of a running
+// trajectory ends it here, as chain_iter_backward_kernel does
+template <int NJ, int NU>
+__global__ __launch_bounds__(CH6_WG) void chain_iter_forward32_kernel(ChainK<double, NJ> P, int B, int T,
+                                                                     ChainIter<double> a,
+                                                                     const int32_t* __restrict__ bstatus,
+                                                                     LSParams ls) {
+  __shared__ ChainK<double, NJ> Ps;
+  __shared__ double stage[(CH6_WG / CH6_LANES) * CH6_STAGE];
+  chain_consts_to_lds(Ps, P);
+  const int b = (blockIdx.x * CH6_WG + threadIdx.x) / CH6_LANES;
+  if (b >= B || a.status[b] != ILQR_TRAJ_OK) return;  // the whole lane group
+  const int l32 = threadIdx.x & (CH6_LANES - 1);
+  if (bstatus[b] != ILQR_TRAJ_OK) {  // reference: AssertionError at backward_pass.jl:353
+    if (l32 == 0) {
+      a.status[b] = ILQR_TRAJ_NAN;
+      if (a.res_parity) a.res_parity[b] = a.parity;
+    }
+    return;
+  }
+  double du2 = 0.0;
+  const double pc = a.prev_cost ? a.prev_cost[b] : (double)INFINITY;
+  const ChainFwdOut<double> r =
+      chain_forward_group32<NJ, NU>(Ps, stage + (threadIdx.x / CH6_LANES) * CH6_STAGE, b, T, a.x, a.u, a.xtraj,
+                                    a.d, a.K, pc, a.xnew, a.unew, &du2, ls);
+  if (l32 != 0) return;
+  if (a.trials) a.trials[b] = r.trials;
+  if (a.du2) a.du2[b] = du2;
+  if (a.iters) a.iters[b] = a.iter;
+  if (!r.accepted) {
+    a.status[b] = (r.cost != r.cost) ? ILQR_TRAJ_NAN : ILQR_TRAJ_LS_EXHAUSTED;
+    if (a.res_parity) a.res_parity[b] = a.parity;
+  } else {
+    a.new_cost[b] = r.cost;                // prev_cost = new_cost (:168)
+    if (du2 <= ls.tol) {                   // (:171) break BEFORE the update
+      a.status[b] = ILQR_TRAJ_CONVERGED;
+      if (a.res_parity) a.res_parity[b] = a.parity;
+    }
+  }
+}
+
 }  // namespace
 }  // namespace ilqr
 
@@ -1919,6 +2413,11 @@ struct ilqr_chain_handle {
   void* K = nullptr;
   void* d = nullptr;
   void* J = nullptr;
+  // six-joint chains: the derivative tiles the wide tiles kernel reads (fp64) and its
+  // per-trajectory status
+  double *tA = nullptr, *tB = nullptr, *lx = nullptr, *lu = nullptr, *lxx = nullptr, *luu = nullptr;
+  double *lfx = nullptr, *lfxx = nullptr;
+  int32_t* bstatus = nullptr;
   void* prev_cost = nullptr;
   void* du2 = nullptr;
   int32_t* trials = nullptr;
@@ -2224,6 +2723,11 @@ struct ChainOps {
         h->batch, h->T, (const V*)h->J, A, Bm);
     return hipGetLastError();
   }
+  // ilqr_chain_linearize: the records, then the caller's A and B
+  static hipError_t linearize_to(ilqr_chain_handle* h, const V* x, const V* u, V* A, V* Bm) {
+    hipError_t e = linearize(h, x, u, nullptr);
+    return e != hipSuccess ? e : unpack(h, A, Bm);
+  }
   static hipError_t backward(ilqr_chain_handle* h, const V* x, const V* u, V* d, V* K,
                              int32_t* st, double mu) {
     hipError_t e = linearize(h, x, u, nullptr);
@@ -2314,15 +2818,111 @@ struct ChainOps {
   }
 };
 
-// (n_joints, nu) shapes with compiled kernels: the iLQR iteration for the 2-DoF arm
-// (nu = 2 every joint driven, nu = 1 joint 1 only); dynamics also for the 6-DoF arm.
+// The six-joint chain (nj = nu = 6, fp64): ChainOps' interface on the tiles path — the
+// linearisation and the costs written as tiles, launch_tiles_backward(12, 6), the 32-lane
+// forward group.
+struct Chain6Ops {
+  static constexpr int NJ = 6, NU = 6, NX = 12;
+  using Value = double;
+  using V = double;
+  using Iter = ilqr::ChainIter<double>;
+
+  static ilqr::ChainCostK<NJ> cost_consts(const ilqr_chain& c) {
+    ilqr::ChainCostK<NJ> C{};
+    for (int i = 0; i < NJ; ++i) {
+      C.tgt[i] = c.target[i];
+      C.qw[i] = c.q_weight[i];
+      C.rw[i] = c.r_weight[i];
+      C.qfw[i] = c.qf_weight[i];
+    }
+    return C;
+  }
+  // lxx, luu, lfxx once per handle (ilqr_chain_create)
+  static hipError_t hessians(ilqr_chain_handle* h) {
+    const size_t n = (size_t)h->batch * (h->T + 1) * NX * NX;
+    ilqr::chain_cost_hessians_kernel<NJ, NU><<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(
+        cost_consts(h->chain), h->batch, h->T, h->lxx, h->luu, h->lfxx);
+    return hipGetLastError();
+  }
+  static hipError_t linearize_to(ilqr_chain_handle* h, const V* x, const V* u, V* A, V* Bm,
+                                 const int32_t* st = nullptr) {
+    const auto P = chain_consts<V, NJ>(h->chain);
+    const size_t lanes = (size_t)h->batch * h->T * (NX + NU);
+    const dim3 grid((unsigned)((lanes + 255) / 256));
+    if (h->lin == ILQR_LINEARIZE_DUAL)
+      ilqr::chain_linearize_tiles_kernel<NJ, NU, ILQR_LINEARIZE_DUAL>
+          <<<grid, 256, 0, h->stream>>>(P, h->batch, h->T, x, u, st, A, Bm);
+    else
+      ilqr::chain_linearize_tiles_kernel<NJ, NU, ILQR_LINEARIZE_CENTRAL_FD>
+          <<<grid, 256, 0, h->stream>>>(P, h->batch, h->T, x, u, st, A, Bm);
+    return hipGetLastError();
+  }
+  // the step's tiles for trajectories with status OK (st null: all)
+  static hipError_t tiles(ilqr_chain_handle* h, const V* x, const V* u, const int32_t* st) {
+    hipError_t e = linearize_to(h, x, u, h->tA, h->tB, st);
+    if (e != hipSuccess) return e;
+    const size_t n = (size_t)h->batch * (h->T + 1) * (NX + NU);
+    ilqr::chain_cost_tiles_kernel<NJ, NU><<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(
+        cost_consts(h->chain), h->batch, h->T, x, u, st, h->lx, h->lu, h->lfx);
+    return hipGetLastError();
+  }
+  static hipError_t dynamics(ilqr_chain_handle* h, const V* x, const V* u, V* xo, int n) {
+    return ChainOps<V, NJ, NU>::dynamics(h, x, u, xo, n);
+  }
+  static ilqr::TileParams tile_params(const ilqr_chain_handle* h) {
+    return ilqr::TileParams{h->tA, h->tB, h->lx, h->lu, h->lxx, nullptr, h->luu, h->lfx, h->lfxx};
+  }
+  static hipError_t backward(ilqr_chain_handle* h, const V* x, const V* u, V* d, V* K, int32_t* st,
+                             double mu) {
+    hipError_t e = tiles(h, x, u, nullptr);
+    if (e != hipSuccess) return e;
+    return ilqr::launch_tiles_backward(NX, NU, tile_params(h), h->batch, h->T, d, K, st ? st : h->bstatus, mu,
+                                       h->stream);
+  }
+  static hipError_t forward(ilqr_chain_handle* h, const V* x, const V* u, const V* xt, const V* d,
+                            const V* K, const V* pc, V* xn, V* un, V* nc, int32_t* tr, int32_t* st,
+                            const ilqr::LSParams& ls) {
+    const auto P = chain_consts<V, NJ>(h->chain);
+    const int grid = (h->batch * ilqr::CH6_LANES + ilqr::CH6_WG - 1) / ilqr::CH6_WG;
+    ilqr::chain_forward32_kernel<NJ, NU><<<grid, ilqr::CH6_WG, 0, h->stream>>>(P, h->batch, h->T, x, u, xt, d, K,
+                                                                             pc, xn, un, nc, tr, st, ls);
+    return hipGetLastError();
+  }
+  static hipError_t iteration(ilqr_chain_handle* h, const Iter& a, const ilqr::LSParams& ls) {
+    hipError_t e = tiles(h, a.x, a.u, a.status);
+    if (e != hipSuccess) return e;
+    // every trajectory runs the recursion (a stopped one on stale tiles, into the handle's
+    // own gains); the forward kernel folds bstatus into the running ones' status
+    e = ilqr::launch_tiles_backward(NX, NU, tile_params(h), h->batch, h->T, a.d, a.K, h->bstatus, ls.mu,
+                                    h->stream);
+    if (e != hipSuccess) return e;
+    const auto P = chain_consts<V, NJ>(h->chain);
+    const int grid = (h->batch * ilqr::CH6_LANES + ilqr::CH6_WG - 1) / ilqr::CH6_WG;
+    ilqr::chain_iter_forward32_kernel<NJ, NU><<<grid, ilqr::CH6_WG, 0, h->stream>>>(P, h->batch, h->T, a,
+                                                                                  h->bstatus, ls);
+    return hipGetLastError();
+  }
+};
+
+// (n_joints, nu) shapes with compiled kernels in every dtype: the iLQR iteration for the
+// 2-DoF arm (nu = 2 every joint driven, nu = 1 joint 1 only); dynamics also for the 6-DoF arm.
 bool iter_supported(int nj, int nu) { return nj == 2 && (nu == 1 || nu == 2); }
 bool dyn_supported(int nj, int nu) { return iter_supported(nj, nu) || (nj == 6 && nu == 6); }
+// ... and per dtype: the 6-DoF arm iterates in fp64 only (its recursion is the f64 MFMA
+// tiles kernel)
+bool iter_supported_dtype(int nj, int nu, int32_t dtype) {
+  if (dtype != ILQR_F32 && dtype != ILQR_F64) return false;
+  return iter_supported(nj, nu) || (nj == 6 && nu == 6 && dtype == ILQR_F64);
+}
+bool handle_iterates(const ilqr_chain_handle* h) { return iter_supported_dtype(h->nj, h->nu, h->dtype); }
 
 template <class V, class Fn>
 hipError_t dispatch(const ilqr_chain_handle* h, Fn&& fn) {
   if (h->nj == 2 && h->nu == 2) return fn(ChainOps<V, 2, 2>{});
   if (h->nj == 2 && h->nu == 1) return fn(ChainOps<V, 2, 1>{});
+  if constexpr (std::is_same_v<V, double>) {
+    if (h->nj == 6 && h->nu == 6) return fn(Chain6Ops{});
+  }
   return hipErrorInvalidValue;
 }
 template <class Fn>
@@ -2443,6 +3043,10 @@ extern "C" {
 
 int ilqr_chain_supported(int n_joints, int nu) { return iter_supported(n_joints, nu) ? 1 : 0; }
 
+int ilqr_chain_supported_dtype(int n_joints, int nu, int32_t dtype) {
+  return iter_supported_dtype(n_joints, nu, dtype) ? 1 : 0;
+}
+
 const char* ilqr_chain_last_error(void) { return g_chain_error.c_str(); }
 
 ilqr_status ilqr_chain_create(ilqr_chain_handle** out, int device, const ilqr_chain* chain, int T,
@@ -2470,14 +3074,35 @@ ilqr_status ilqr_chain_create(ilqr_chain_handle** out, int device, const ilqr_ch
   h->created = *chain;
   const size_t w = vsize(h), B = (size_t)batch, nx = 2 * (size_t)h->nj, nu = (size_t)h->nu;
   hipError_t e = hipSuccess;
-  if (iter_supported(h->nj, h->nu)) {  // dynamics-only shapes need no workspace
+  const bool six = h->nj == 6;
+  if (handle_iterates(h)) {  // dynamics-only shapes need no workspace
     for (int i = 0; i < 2 && e == hipSuccess; ++i) {
       e = hipMalloc(&h->xbuf[i], w * B * (T + 1) * nx);
       if (e == hipSuccess) e = hipMalloc(&h->ubuf[i], w * B * T * nu);
     }
     if (e == hipSuccess) e = hipMalloc(&h->K, w * B * T * nu * nx);
     if (e == hipSuccess) e = hipMalloc(&h->d, w * B * T * nu);
-    if (e == hipSuccess) e = hipMalloc(&h->J, w * B * T * (nx * (nx + nu) + nx + nu));
+    if (e == hipSuccess && !six) e = hipMalloc(&h->J, w * B * T * (nx * (nx + nu) + nx + nu));
+    if (six) {  // the tiles in place of the records
+      auto tile = [&](double** p, size_t n) {
+        if (e == hipSuccess) e = hipMalloc(p, sizeof(double) * n);
+      };
+      tile(&h->tA, B * T * nx * nx);
+      tile(&h->tB, B * T * nx * nu);
+      tile(&h->lx, B * T * nx);
+      tile(&h->lu, B * T * nu);
+      tile(&h->lxx, B * T * nx * nx);
+      tile(&h->luu, B * T * nu * nu);
+      tile(&h->lfx, B * nx);
+      tile(&h->lfxx, B * nx * nx);
+      if (e == hipSuccess) e = hipMalloc(&h->bstatus, sizeof(int32_t) * B);
+      // stopped trajectories run the recursion on whatever their tiles hold: keep it defined
+      if (e == hipSuccess) e = hipMemset(h->tA, 0, sizeof(double) * B * T * nx * nx);
+      if (e == hipSuccess) e = hipMemset(h->tB, 0, sizeof(double) * B * T * nx * nu);
+      if (e == hipSuccess) e = hipMemset(h->lx, 0, sizeof(double) * B * T * nx);
+      if (e == hipSuccess) e = hipMemset(h->lu, 0, sizeof(double) * B * T * nu);
+      if (e == hipSuccess) e = hipMemset(h->lfx, 0, sizeof(double) * B * nx);
+    }
     if (e == hipSuccess) e = hipMalloc(&h->prev_cost, w * B);
     if (e == hipSuccess) e = hipMalloc(&h->du2, w * B);
     if (e == hipSuccess) e = hipMalloc(&h->trials, sizeof(int32_t) * B);
@@ -2498,6 +3123,14 @@ ilqr_status ilqr_chain_create(ilqr_chain_handle** out, int device, const ilqr_ch
   if (iter_supported(h->nj, h->nu) && (e = chain_trig_build(h)) != hipSuccess) {
     ilqr_chain_destroy(h);
     return chain_hip_fail(e, "ilqr_chain_create: closed-form dynamics");
+  }
+  if (six && handle_iterates(h)) {
+    e = Chain6Ops::hessians(h);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+      ilqr_chain_destroy(h);
+      return chain_hip_fail(e, "ilqr_chain_create: cost tiles");
+    }
   }
   *out = h;
   return ILQR_OK;
@@ -2577,6 +3210,8 @@ ilqr_status ilqr_chain_destroy(ilqr_chain_handle* h) {
     (void)hipFree(h->ubuf[i]);
   }
   for (void* p : {h->K, h->d, h->J, h->prev_cost, h->du2}) (void)hipFree(p);
+  for (double* p : {h->tA, h->tB, h->lx, h->lu, h->lxx, h->luu, h->lfx, h->lfxx}) (void)hipFree(p);
+  (void)hipFree(h->bstatus);
   for (int32_t* p : {h->trials, h->status, h->res_parity, h->iters, h->dev_flags}) (void)hipFree(p);
   if (h->host_words) (void)hipHostFree(h->host_words);
   for (hipEvent_t ev : h->ev_poll)
@@ -2615,13 +3250,12 @@ ilqr_status ilqr_chain_dynamics(ilqr_chain_handle* h, const void* x, const void*
 ilqr_status ilqr_chain_linearize(ilqr_chain_handle* h, const void* x, const void* u, void* A,
                                  void* B) {
   if (!h || !x || !u || !A || !B) return ILQR_ERR_BAD_ARG;
-  if (!iter_supported(h->nj, h->nu)) return ILQR_ERR_UNSUPPORTED;
+  if (!handle_iterates(h)) return ILQR_ERR_UNSUPPORTED;
   CH_TRY(hipSetDevice(h->device));
   CH_TRY(dispatch_any(h, [&](auto ops) {
     using O = decltype(ops);
     using V = typename O::Value;
-    hipError_t e = O::linearize(h, (const V*)x, (const V*)u, nullptr);
-    return e != hipSuccess ? e : O::unpack(h, (V*)A, (V*)B);
+    return O::linearize_to(h, (const V*)x, (const V*)u, (V*)A, (V*)B);
   }));
   return ILQR_OK;
 }
@@ -2629,7 +3263,7 @@ ilqr_status ilqr_chain_linearize(ilqr_chain_handle* h, const void* x, const void
 ilqr_status ilqr_chain_backward(ilqr_chain_handle* h, const ilqr_options* o, const void* x,
                                 const void* u, void* d, void* K, int32_t* status) {
   if (!h || !x || !u || !d || !K) return ILQR_ERR_BAD_ARG;
-  if (!iter_supported(h->nj, h->nu)) return ILQR_ERR_UNSUPPORTED;
+  if (!handle_iterates(h)) return ILQR_ERR_UNSUPPORTED;
   ilqr_status st = chain_check_options(o);
   if (st != ILQR_OK) return st;
   CH_TRY(hipSetDevice(h->device));
@@ -2648,7 +3282,7 @@ ilqr_status ilqr_chain_forward(ilqr_chain_handle* h, const ilqr_options* o, cons
                                int32_t* trials, int32_t* status) {
   if (!h || !x || !u || !d || !K || !prev_cost || !x_new || !u_new || !new_cost)
     return ILQR_ERR_BAD_ARG;
-  if (!iter_supported(h->nj, h->nu)) return ILQR_ERR_UNSUPPORTED;
+  if (!handle_iterates(h)) return ILQR_ERR_UNSUPPORTED;
   ilqr_status st = chain_check_options(o);
   if (st != ILQR_OK) return st;
   CH_TRY(hipSetDevice(h->device));
@@ -2667,7 +3301,7 @@ ilqr_status ilqr_chain_iterate(ilqr_chain_handle* h, const ilqr_options* o, cons
                                const void* prev_cost, void* new_cost, void* du2, int32_t* trials,
                                int32_t* status) {
   if (!h || !x || !u || !x_new || !u_new || !new_cost || !status) return ILQR_ERR_BAD_ARG;
-  if (!iter_supported(h->nj, h->nu)) return ILQR_ERR_UNSUPPORTED;
+  if (!handle_iterates(h)) return ILQR_ERR_UNSUPPORTED;
   ilqr_status st = chain_check_options(o);
   if (st != ILQR_OK) return st;
   CH_TRY(hipSetDevice(h->device));
@@ -2693,7 +3327,7 @@ ilqr_status ilqr_chain_fit_ex(ilqr_chain_handle* h, const ilqr_options* o, const
                               void* cost, int32_t* iters, int32_t* status, const ilqr_history* hist) {
   if (!h || !x_init || !u_init || !x_out || !u_out) return ILQR_ERR_BAD_ARG;
   if (hist && !hist->cost && !hist->trials && !hist->alpha && !hist->du2) hist = nullptr;
-  if (!iter_supported(h->nj, h->nu)) return ILQR_ERR_UNSUPPORTED;
+  if (!handle_iterates(h)) return ILQR_ERR_UNSUPPORTED;
   ilqr_status st = chain_check_options(o);
   if (st != ILQR_OK) return st;
   CH_TRY(hipSetDevice(h->device));

@@ -9,8 +9,8 @@ __all__ = ["LinearDynamics", "QuadraticCost", "QuadraticFinalCost", "LQBatch",
            "lq_from_closures", "TwoLinkArm", "TwoLinkDynamics", "TwoLinkDynamicsNu1", "TwoLinkCost",
            "TwoLinkFinalCost", "two_link_closures", "two_link_initial_states", "quadrotor_batch", "quadrotor_instance", "random_lq_batch",
            "fit", "backward_pass", "forward_pass", "Solver", "selftest", "LineSearchExhausted",
-           "ChainSolver", "ChainProblem", "rbd_2dof_problem", "chain_closures", "load_robot",
-           "rbd_initial_states", "simple_final_cost", "simple_immediate_cost",
+           "ChainSolver", "ChainProblem", "rbd_2dof_problem", "rbd_6dof_problem", "chain_closures",
+           "load_robot", "rbd_initial_states", "simple_final_cost", "simple_immediate_cost",
            "linearize_dynamics", "immediate_cost_quadratization", "final_cost_quadratization",
            "optimal_controller_param", "feedback_parameters", "step_back",
            "FloatingSolver", "FloatingProblem", "rbd_example_problem", "floating_closures"]
@@ -28,8 +28,8 @@ def __getattr__(name):
     if name in _HELPERS:  # the reference's documented per-step API (docs/src/documentation.md)
         from . import helpers
         return getattr(helpers, name)
-    if name in ("ChainSolver", "ChainProblem", "rbd_2dof_problem", "chain_closures", "load_robot",
-                "rbd_initial_states"):
+    if name in ("ChainSolver", "ChainProblem", "rbd_2dof_problem", "rbd_6dof_problem", "chain_closures",
+                "load_robot", "rbd_initial_states"):
         from . import chain
         return getattr(chain, name)
     if name in ("FloatingSolver", "FloatingProblem", "rbd_example_problem", "floating_closures"):

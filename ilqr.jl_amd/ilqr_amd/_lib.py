@@ -151,6 +151,7 @@ SIGNATURES = {
     "ilqr_memcpy_d2h": (C.c_int, [P, P, P, C.c_size_t]),
     "ilqr_selftest": (C.c_int, [C.c_int, C.POINTER(C.c_int32)]),
     "ilqr_chain_supported": (C.c_int, [C.c_int, C.c_int]),
+    "ilqr_chain_supported_dtype": (C.c_int, [C.c_int, C.c_int, C.c_int32]),
     "ilqr_chain_last_error": (C.c_char_p, []),
     "ilqr_chain_create": (C.c_int, [C.POINTER(P), C.c_int, C.POINTER(ChainStruct), C.c_int,
                                     C.c_int, C.c_int32, C.c_int32]),

@@ -102,6 +102,12 @@ def _chain_solver(xb, ub, dynamicsf, immediate_cost, final_cost, dtype):
     p = chain_problem_of(dynamicsf, immediate_cost, final_cost)
     if (p.nx, p.nu) != (nx, nu):
         raise AssertionError(f"problem is ({p.nx}, {p.nu}) but x/u are ({nx}, {nu})")
+    lib = _lib.load()
+    if (dtype == torch.float32 and not lib.ilqr_chain_supported_dtype(p.n_joints, p.nu, _lib.F32)
+            and lib.ilqr_chain_supported_dtype(p.n_joints, p.nu, _lib.F64)):
+        # no silent promotion: the element type decides the arithmetic (the reference's rule)
+        raise ValueError(f"a {p.n_joints}-joint chain is solved in fp64 only (float64 inputs); "
+                         "got float32 x / u")
     s = ChainSolver(p, M, nb, dtype=dtype, device=_device())
     fc = simple_costs_of(p, immediate_cost, final_cost)   # cost_functions.jl's factories
     if fc is not None:

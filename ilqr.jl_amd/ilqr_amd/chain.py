@@ -16,6 +16,7 @@ solver's dtype (float32 or float64), laid out as include/ilqr.h documents.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import json
 import math
 import os
@@ -129,6 +130,20 @@ def coupled_2dof_problem(nu: int = 2) -> ChainProblem:
     return ChainProblem(chain, nu, RBD_DT, RBD_TARGET_JOINTS, RBD_Q_JOINT, RBD_R_JOINT, RBD_QF_JOINT)
 
 
+RBD_TARGET_JOINTS_6DOF = (0.5, -0.4, 0.3, 0.6, -0.2, 0.4)
+
+
+def rbd_6dof_problem(gravity: bool = False) -> ChainProblem:
+    """The RBD example's joint-space costs on the shipped 6Dof_arm with a fixed base, every
+    joint driven (fp64 iteration kernels). The URDF parses with zero gravity, as the
+    reference loads it; gravity=True sets (0, 0, −9.81) on a copy of the chain, which
+    makes ∂q̈/∂q nonzero from rest."""
+    ch = load_robot("6dof_arm")
+    if gravity:
+        ch = dataclasses.replace(ch, gravity=np.array([0.0, 0.0, -9.81]))
+    return ChainProblem(ch, 6, RBD_DT, RBD_TARGET_JOINTS_6DOF, RBD_Q_JOINT, RBD_R_JOINT, RBD_QF_JOINT)
+
+
 def rbd_initial_states(batch: int, n_joints: int = 2, seed0: int = 0):
     """x₀[b] = [q ~ U(−1, 1)^n, q̇ = 0] from numpy.random.default_rng(seed0 + b)."""
     x0 = np.zeros((batch, 2 * n_joints))
@@ -159,12 +174,15 @@ class ChainSolver:
                                               _lib.F32 if dtype == torch.float32 else _lib.F64,
                                               _LIN[linearization]), "ilqr_chain_create")
         self.h = h
-        self.iterates = bool(self.lib.ilqr_chain_supported(self.nj, self.nu))
+        # the iteration kernels of this shape in the solver's dtype (the 6-DoF arm: fp64 only)
+        self.iterates = bool(self.lib.ilqr_chain_supported_dtype(
+            self.nj, self.nu, _lib.F32 if dtype == torch.float32 else _lib.F64))
 
     def set_dynamics(self, mode: str):
         """The iteration kernels' dynamics evaluator (2-joint chains): "auto" (the closed
         form when its creation check passed), "rnea" (the recursive Newton-Euler, the
-        restatement of RigidBodyDynamics.jl's calls) or "closed_form"."""
+        restatement of RigidBodyDynamics.jl's calls) or "closed_form". Six joints run the
+        recursion: "auto" and "rnea" mean the same, "closed_form" is unsupported."""
         m = {"auto": _lib.CHAIN_DYN_AUTO, "rnea": _lib.CHAIN_DYN_RNEA,
              "closed_form": _lib.CHAIN_DYN_CLOSED_FORM}[mode]
         _lib.check(self.lib.ilqr_chain_set_dynamics(self.h, m), "ilqr_chain_set_dynamics")

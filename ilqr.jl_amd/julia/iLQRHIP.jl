@@ -916,7 +916,10 @@ Array{Float32,3} (fp32, BASELINE config 5) or Array{Float64,3}: the element type
 the device precision, as the reference's generic Julia code would. `dynamics` picks the
 2-joint evaluator (AUTO: the closed form sampled from the Newton-Euler recursion at
 creation; RNEA: the recursion itself). `costs = simple_costs(…)` replaces the chain's
-joint-space costs with cost_functions.jl's pair (2-joint chains, closed form). The handle
+joint-space costs with cost_functions.jl's pair (2-joint chains, closed form). Nothing here
+depends on the joint count: the 6-DoF arm (n_joints = nu = 6) iterates in fp64
+(ilqr_chain_supported_dtype(6, 6, ILQR_F64) == 1), so it takes Array{Float64,3}; with
+Array{Float32,3} ilqr_chain_fit returns ILQR_ERR_UNSUPPORTED. The handle
 and buffers are cached per (chain, T, batch, element type, options): an MPC loop calling
 chain_fit allocates nothing per call (clear_cache!() closes them)."""
 function chain_fit(c::Chain, x_init::Array{E,3}, u_init::Array{E,3}; max_iter::Int64=100,

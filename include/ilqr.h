@@ -128,7 +128,9 @@ const char* ilqr_status_string(ilqr_status s);
 /* last HIP error text recorded by this thread (empty string if none) */
 const char* ilqr_last_error(void);
 void ilqr_default_options(ilqr_options* opts);
-/* 1 if (nx, nu) has a compiled kernel for `kind` */
+/* 1 if (nx, nu) has a compiled kernel for `kind`. ILQR_PROBLEM_CHAIN answers through
+ * ilqr_chain_supported (every dtype), so (12, 6) — the 6-DoF arm, fp64 only — is 0 here:
+ * ask ilqr_chain_supported_dtype. */
 int ilqr_supported(int32_t kind, int nx, int nu);
 
 /* Bind a handle to `device`, preallocating the workspace (trajectory ping-pong
@@ -291,8 +293,18 @@ ilqr_status ilqr_fit_ex(ilqr_handle* h, const ilqr_problem* p, const ilqr_option
  * above in the handle's dtype (ILQR_F32 or ILQR_F64), costs included; the
  * derivatives of dynamicsf are forward-mode duals (ForwardDiff's algorithm,
  * ILQR_LINEARIZE_DUAL) or central differences (ILQR_LINEARIZE_CENTRAL_FD).
- * Compiled shapes: ilqr_chain_supported(); ilqr_chain_dynamics also takes the
- * 6-DoF arm (n_joints = nu = 6).
+ * Compiled shapes (ilqr_chain_supported_dtype): the 2-joint arm with nu = 1 or 2 in
+ * either dtype, and the 6-DoF arm (n_joints = nu = 6) in ILQR_F64 — every entry point,
+ * both linearisations, the argument, status, NaN and line-search semantics of the
+ * 2-joint family. A six-joint ILQR_F32 handle answers ilqr_chain_dynamics only (the rest
+ * returns ILQR_ERR_UNSUPPORTED); (6, 1) is not compiled. Six joints run the recursive
+ * Newton-Euler only: ilqr_chain_set_simple_costs and ilqr_chain_set_dynamics(CLOSED_FORM)
+ * return ILQR_ERR_UNSUPPORTED, AUTO and RNEA both mean the recursion.
+ * Device memory taken at creation, per (trajectory, step): a 2-joint handle keeps one
+ * linearisation record (nx(nx + nu) + nx + nu words), a six-joint fp64 handle the tiles
+ * of the wide Riccati kernel instead — A 144, B 72, lxx 144, luu 36, lx 12, lu 6 doubles —
+ * plus, for both, the gains (nu·nx + nu) and two trajectory buffers (2(nx + nu)):
+ * 528 doubles = 4224 bytes per (trajectory, step) for six joints.
  * --------------------------------------------------------------------------- */
 #define ILQR_CHAIN_MAX_JOINTS 8
 
@@ -318,8 +330,13 @@ typedef struct {
 
 typedef struct ilqr_chain_handle ilqr_chain_handle;
 
-/* 1 if the iLQR kernels are compiled for (n_joints, nu) */
+/* 1 if the iteration kernels are compiled for this shape in EVERY dtype: (2, 1) and
+ * (2, 2). 0 for the 6-DoF arm, which iterates in fp64 only. */
 int ilqr_chain_supported(int n_joints, int nu);
+/* 1 if the iteration kernels (linearize, backward, forward, iterate, fit) are compiled
+ * for this shape in `dtype`: (2, 1 or 2) in ILQR_F32 and ILQR_F64, (6, 6) in ILQR_F64.
+ * 0 otherwise, an invalid dtype included. */
+int ilqr_chain_supported_dtype(int n_joints, int nu, int32_t dtype);
 const char* ilqr_chain_last_error(void);
 ilqr_status ilqr_chain_create(ilqr_chain_handle** out, int device, const ilqr_chain* chain, int T,
                               int batch, int32_t dtype, int32_t linearization);

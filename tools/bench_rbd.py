@@ -1,4 +1,5 @@
-"""Secondary benchmark: BASELINE config 5 — the RBD example (RigidBodyDynamics-style
+"""Secondary benchmark (--robot 6dof_arm: the same step on the shipped 6-DoF arm, nx = 12,
+nu = 6, fp64): BASELINE config 5 — the RBD example (RigidBodyDynamics-style
 dynamics of test/urdf/2Dof_arm.urdf, fixed base: nx = 4, nu = 1 as the config states, or
 --nu 2), T = 100,
 batch 2048 random x₀, fp32, linearised on the device by central finite differences
@@ -23,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "ilqr.jl_amd")]
 
 from ilqr_amd import _lib  # noqa: E402
-from ilqr_amd.chain import ChainSolver, rbd_2dof_problem, rbd_initial_states  # noqa: E402
+from ilqr_amd.chain import ChainSolver, rbd_2dof_problem, rbd_6dof_problem, rbd_initial_states  # noqa: E402
 from tools import flops as FL  # noqa: E402
 
 PEAK_TFLOPS = {"f32": 157.3, "f64": 78.6}   # MI355X vector FP32 / FP64 (spec; MI355X_MICROARCH.md)
@@ -72,7 +73,7 @@ def measure(lin="fd", B=2048, T=100, nu=1, dtype="f32", steps=100, warmup=100, d
     # problem: another chain (the coupled 2-joint test chain: q-dependent M and bias, which
     # the reference's 2Dof_arm.urdf parses without — constant M, zero bias)
     pr = rbd_2dof_problem(nu) if problem is None else problem
-    x0 = rbd_initial_states(B, 2)
+    x0 = rbd_initial_states(B, pr.n_joints)
     s = ChainSolver(pr, T, B, dtype=dt, linearization=lin, device=device)
     s.set_dynamics(dynamics)
     u = torch.zeros((B, T, pr.nu), dtype=dt, device=dev)
@@ -123,12 +124,15 @@ def measure(lin="fd", B=2048, T=100, nu=1, dtype="f32", steps=100, warmup=100, d
     ric_fl = FL.riccati_flops_per_step(pr.nx, pr.nu) * T * B
     fw_fl = FL.forward_flops_per_step(pr.nx, pr.nu, f_rk4) * T * B
     peak = PEAK_TFLOPS[dtype]
+    # lanes per trajectory of the forward that runs: 4 line-search candidates on the closed
+    # form, a 16-lane Newton-Euler group on the 2-joint recursion, 32 lanes for six joints
+    fw_lanes = 4 if s.dynamics_mode == "closed_form" else (16 if pr.n_joints <= 3 else 32)
     kern = {"linearize": (lin_ms, lin_fl), "riccati": (max(bw_ms - lin_ms, 1e-6), ric_fl),
             "forward": (fw_ms, fw_fl)}
     roof = {"bound": ("forward latency/issue (a dependent RK4 chain per trajectory, 4 candidate lanes each, "
                       "closed-form dynamics)"
                       if s.dynamics_mode == "closed_form" else
-                      "forward latency/issue (16 lanes per trajectory)") + ", linearisation VALU issue",
+                      f"forward latency/issue ({fw_lanes} lanes per trajectory)") + ", linearisation VALU issue",
             "unit": "TFLOP/s", "peak": peak, "peak_dtype": dtype,
             "flops_note": (f"RK4 of the closed form = {f_rk4} flop; of the restated RBD recursion "
                            f"(the reference's RigidBodyDynamics.jl calls) = {f_ref} flop (tools/flops.py)"
@@ -142,13 +146,16 @@ def measure(lin="fd", B=2048, T=100, nu=1, dtype="f32", steps=100, warmup=100, d
     # candidate lanes each: 4B of the chip's 65,536 lanes), so its time is T × the
     # latency of one step — the FLOP fraction is small by construction
     roof["forward"]["step_latency_ns"] = fw_ms * 1e6 / T
-    roof["forward"]["lanes_busy_frac"] = min(1.0, 4 * B / (1024 * 64))
-    res = {"metric": f"batched iLQR iterations/sec (fwd+bwd pass), RBD 2-DoF arm fixed base, "
-                     f"nx=4 nu={pr.nu} T={T}",
+    roof["forward"]["lanes_busy_frac"] = min(1.0, (4 if pr.n_joints == 2 else fw_lanes) * B / (1024 * 64))
+    six = pr.n_joints != 2
+    res = {"metric": f"batched iLQR iterations/sec (fwd+bwd pass), RBD {pr.n_joints}-DoF arm fixed base, "
+                     f"nx={pr.nx} nu={pr.nu} T={T}",
            "value": 1000.0 / ms, "unit": f"batched iterations/s (batch={B})", "n_gpus": 1,
            "steps": steps, "warmup": warmup, "ms_per_step": ms,
            "higher_is_better": True, "dtype": dtype, "data": "synthetic x0 ~ U(-1,1)",
-           "config": {"workload": "BASELINE config 5 (RBD_2_link_example, fixed base)",
+           "config": {"workload": (f"the RBD example's costs on the shipped {pr.n_joints}-DoF arm (fixed base, "
+                                   f"gravity {[float(v) for v in pr.chain.gravity]})" if six else
+                                   "BASELINE config 5 (RBD_2_link_example, fixed base)"),
                       "batch": B, "T": T, "linearization": lin, "dynamics": s.dynamics_mode,
                       "closed_form_check": s.closed_form_error},
            "traj_iters_per_s": B * 1000.0 / ms,
@@ -163,6 +170,8 @@ def measure(lin="fd", B=2048, T=100, nu=1, dtype="f32", steps=100, warmup=100, d
             base["value"] = base["value"] / B  # trajectory-iterations/s → batched it/s
             base["unit"] = f"batched iterations/s (batch={B})"
         res["cpu_baseline"] = base
+        if six:  # the rate against the C restatement's, from this same run
+            res["ratio_to_cpu_baseline"] = res["value"] / base["value"]
     res["fit"] = fit_timing(s, x, u)
     s.close()
     return res
@@ -199,13 +208,24 @@ def main():
     ap.add_argument("--lin", default="fd,dual")
     ap.add_argument("--cpu-budget", type=float, default=10.0)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--robot", default="2dof_arm", choices=["2dof_arm", "6dof_arm"],
+                    help="6dof_arm: every joint driven (nu = 6), --dtype f64 only")
+    ap.add_argument("--gravity", action="store_true", help="6dof_arm: gravity (0, 0, -9.81) on")
     ap.add_argument("--dynamics", default="auto", choices=["auto", "rnea", "closed_form"],
                     help="the chain handle's dynamics evaluator (ilqr_chain_set_dynamics)")
     args = ap.parse_args()
     base = None
+    problem = None
+    if args.robot == "6dof_arm":
+        if args.dtype != "f64":
+            ap.error("--robot 6dof_arm runs --dtype f64 only (its iteration kernels are fp64)")
+        problem = rbd_6dof_problem(gravity=args.gravity)
+    elif args.gravity:
+        ap.error("--gravity goes with --robot 6dof_arm")
     for lin in args.lin.split(","):
         res = measure(lin, args.batch, args.T, args.nu, args.dtype, args.steps, args.warmup,
-                      dynamics=args.dynamics, cpu_budget=None if args.no_cpu else args.cpu_budget, base=base)
+                      dynamics=args.dynamics, cpu_budget=None if args.no_cpu else args.cpu_budget, base=base,
+                      problem=problem)
         base = res["cpu_baseline"]
         print(json.dumps(res), flush=True)
 
