@@ -91,6 +91,40 @@ struct ilqr_handle {
   hipEvent_t ev_fw[2] = {nullptr, nullptr};
 };
 
+namespace ilqr {
+
+LSParams ls_params(const ilqr_options* o) {
+  ilqr_options def;
+  ilqr_default_options(&def);
+  if (!o) o = &def;
+  return LSParams{o->mu, o->alpha0, o->shrink, o->tol, o->max_trials};
+}
+
+ilqr_status check_options(const ilqr_options* o) {
+  if (!o) return ILQR_OK;
+  if (o->max_trials < 1 || o->max_iter < 0) return ILQR_ERR_BAD_ARG;
+  if (!(o->shrink > 0.0 && o->shrink < 1.0) || !(o->alpha0 > 0.0) || std::isnan(o->mu))
+    return ILQR_ERR_BAD_ARG;
+  return ILQR_OK;
+}
+
+hipError_t fold_status(const int32_t* dev_status, int n, hipStream_t s, int32_t* host, ilqr_status* out) {
+  std::vector<int32_t> tmp(host ? 0 : n);
+  int32_t* st = host ? host : tmp.data();  // a pinned `host`: one DMA, no staging copy
+  hipError_t e = hipMemcpyAsync(st, dev_status, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return e;
+  bool nan = false, ls = false;
+  for (int b = 0; b < n; ++b) {
+    nan |= st[b] == ILQR_TRAJ_NAN;
+    ls |= st[b] == ILQR_TRAJ_LS_EXHAUSTED;
+  }
+  *out = nan ? ILQR_ERR_NAN : (ls ? ILQR_ERR_LS_EXHAUSTED : ILQR_OK);
+  return hipSuccess;
+}
+
+}  // namespace ilqr
+
 namespace {
 
 thread_local std::string g_last_error;
@@ -137,13 +171,6 @@ bool two_link(const ilqr_problem* p) { return p->kind == ILQR_PROBLEM_TWO_LINK; 
 
 bool padded(const ilqr_handle* h, const ilqr_problem* p) {
   return p->kind == ILQR_PROBLEM_LQ && lq_paddable(h->nx, h->nu);
-}
-
-ilqr::LSParams ls_params(const ilqr_options* o) {
-  ilqr_options def;
-  ilqr_default_options(&def);
-  if (!o) o = &def;
-  return ilqr::LSParams{o->mu, o->alpha0, o->shrink, o->tol, o->max_trials};
 }
 
 ilqr_status join(ilqr_handle* h, const ilqr_problem* p);
@@ -210,27 +237,6 @@ ilqr_status join(ilqr_handle* h, const ilqr_problem* p) {
   if (two_link(p) || h->nchunks == 1) return ILQR_OK;
   for (int c = 0; c < h->nchunks; ++c) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_fw[c], 0));
   return ILQR_OK;
-}
-
-ilqr_status check_options(const ilqr_options* o) {
-  if (!o) return ILQR_OK;
-  if (o->max_trials < 1 || o->max_iter < 0) return ILQR_ERR_BAD_ARG;
-  if (!(o->shrink > 0.0 && o->shrink < 1.0) || !(o->alpha0 > 0.0) || std::isnan(o->mu))
-    return ILQR_ERR_BAD_ARG;
-  return ILQR_OK;
-}
-
-// Reduce per-trajectory status to the call status (host copy, synchronising).
-ilqr_status fold_status(ilqr_handle* h, const int32_t* dev_status) {
-  int32_t* st = h->host_status;  // pinned: one DMA, no staging copy
-  HIP_TRY(hipMemcpyAsync(st, dev_status, sizeof(int32_t) * h->batch, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  bool nan = false, ls = false;
-  for (int b = 0; b < h->batch; ++b) {
-    nan |= st[b] == ILQR_TRAJ_NAN;
-    ls |= st[b] == ILQR_TRAJ_LS_EXHAUSTED;
-  }
-  return nan ? ILQR_ERR_NAN : (ls ? ILQR_ERR_LS_EXHAUSTED : ILQR_OK);
 }
 
 // Inner (12, 4) handle and padded scratch, created on the first padded call (the
@@ -571,7 +577,7 @@ ilqr_status ilqr_backward(ilqr_handle* h, const ilqr_problem* p, const ilqr_opti
                           int32_t* status) {
   ilqr_status st = check_problem(h, p);
   if (st != ILQR_OK) return st;
-  if ((st = check_options(o)) != ILQR_OK) return st;
+  if ((st = ilqr::check_options(o)) != ILQR_OK) return st;
   if (!x || !u || !d || !K) return ILQR_ERR_BAD_ARG;
   HIP_TRY(hipSetDevice(h->device));
   if (padded(h, p)) {
@@ -590,17 +596,18 @@ ilqr_status ilqr_backward(ilqr_handle* h, const ilqr_problem* p, const ilqr_opti
   }
   if (two_link(p))
     HIP_TRY(ilqr::launch_tl_backward(ilqr::two_link_params(), h->nu, h->batch, h->T, x, u, h->J, d, K,
-                                     status, ls_params(o).mu, h->stream));
+                                     status, ilqr::ls_params(o).mu, h->stream));
   else
     HIP_TRY(ilqr::launch_lq_backward(h->nx, h->nu, lq_params(p), h->batch, h->T, x, u, d, K,
-                                     status, ls_params(o).mu, h->stream, h->bw_wave));
-  return status ? fold_status(h, status) : ILQR_OK;
+                                     status, ilqr::ls_params(o).mu, h->stream, h->bw_wave));
+  if (status) HIP_TRY(ilqr::fold_status(status, h->batch, h->stream, h->host_status, &st));
+  return st;
 }
 
 ilqr_status ilqr_backward_tiles(ilqr_handle* h, const ilqr_tiles* tl, const ilqr_options* o,
                                 double* d, double* K, int32_t* status) {
   if (!h || !tl) return ILQR_ERR_BAD_ARG;
-  ilqr_status st = check_options(o);
+  ilqr_status st = ilqr::check_options(o);
   if (st != ILQR_OK) return st;
   if (!ilqr::tiles_supported(h->nx, h->nu)) return ILQR_ERR_UNSUPPORTED;
   if (!tl->A || !tl->B || !tl->lx || !tl->lu || !tl->lxx || !tl->luu || !tl->lfx || !tl->lfxx ||
@@ -609,8 +616,9 @@ ilqr_status ilqr_backward_tiles(ilqr_handle* h, const ilqr_tiles* tl, const ilqr
   HIP_TRY(hipSetDevice(h->device));
   const ilqr::TileParams P{tl->A, tl->B, tl->lx, tl->lu, tl->lxx, tl->lux, tl->luu, tl->lfx, tl->lfxx};
   HIP_TRY(ilqr::launch_tiles_backward(h->nx, h->nu, P, h->batch, h->T, d, K, status,
-                                      ls_params(o).mu, h->stream));
-  return status ? fold_status(h, status) : ILQR_OK;
+                                      ilqr::ls_params(o).mu, h->stream));
+  if (status) HIP_TRY(ilqr::fold_status(status, h->batch, h->stream, h->host_status, &st));
+  return st;
 }
 
 ilqr_status ilqr_linearize(ilqr_handle* h, const ilqr_problem* p, const double* x, const double* u,
@@ -635,7 +643,7 @@ ilqr_status ilqr_forward(ilqr_handle* h, const ilqr_problem* p, const ilqr_optio
                          int32_t* status) {
   ilqr_status st = check_problem(h, p);
   if (st != ILQR_OK) return st;
-  if ((st = check_options(o)) != ILQR_OK) return st;
+  if ((st = ilqr::check_options(o)) != ILQR_OK) return st;
   if (!x || !u || !d || !K || !prev_cost || !x_new || !u_new || !new_cost) return ILQR_ERR_BAD_ARG;
   HIP_TRY(hipSetDevice(h->device));
   if (padded(h, p)) {
@@ -659,12 +667,13 @@ ilqr_status ilqr_forward(ilqr_handle* h, const ilqr_problem* p, const ilqr_optio
   if (two_link(p))
     HIP_TRY(ilqr::launch_tl_forward(ilqr::two_link_params(), h->nu, h->batch, h->T, x, u, x_traj, d, K,
                                     prev_cost, x_new, u_new, new_cost, trials, status,
-                                    ls_params(o), h->stream));
+                                    ilqr::ls_params(o), h->stream));
   else
     HIP_TRY(ilqr::launch_lq_forward(h->nx, h->nu, lq_params(p), h->batch, h->T, x, u, x_traj, d,
                                     K, prev_cost, x_new, u_new, new_cost, trials, status,
-                                    ls_params(o), h->stream, h->fw_ring, h->fw_mfma));
-  return status ? fold_status(h, status) : ILQR_OK;
+                                    ilqr::ls_params(o), h->stream, h->fw_ring, h->fw_mfma));
+  if (status) HIP_TRY(ilqr::fold_status(status, h->batch, h->stream, h->host_status, &st));
+  return st;
 }
 
 ilqr_status ilqr_iterate(ilqr_handle* h, const ilqr_problem* p, const ilqr_options* o,
@@ -674,7 +683,7 @@ ilqr_status ilqr_iterate(ilqr_handle* h, const ilqr_problem* p, const ilqr_optio
                          int32_t* status) {
   ilqr_status st = check_problem(h, p);
   if (st != ILQR_OK) return st;
-  if ((st = check_options(o)) != ILQR_OK) return st;
+  if ((st = ilqr::check_options(o)) != ILQR_OK) return st;
   if (!x || !u || !x_new || !u_new || !new_cost || !status) return ILQR_ERR_BAD_ARG;
   HIP_TRY(hipSetDevice(h->device));
   if (padded(h, p)) {
@@ -706,7 +715,7 @@ ilqr_status ilqr_iterate(ilqr_handle* h, const ilqr_problem* p, const ilqr_optio
   a.iters = nullptr;
   a.parity = 0;
   a.iter = 0;
-  return enqueue_iteration(h, p, a, ls_params(o), /*chain=*/false);
+  return enqueue_iteration(h, p, a, ilqr::ls_params(o), /*chain=*/false);
 }
 
 ilqr_status ilqr_fit(ilqr_handle* h, const ilqr_problem* p, const ilqr_options* o,
@@ -723,7 +732,7 @@ ilqr_status ilqr_fit_ex(ilqr_handle* h, const ilqr_problem* p, const ilqr_option
   if (hist && !hist->cost && !hist->trials && !hist->alpha && !hist->du2) hist = nullptr;
   ilqr_status st = check_problem(h, p);
   if (st != ILQR_OK) return st;
-  if ((st = check_options(o)) != ILQR_OK) return st;
+  if ((st = ilqr::check_options(o)) != ILQR_OK) return st;
   if (!x_init || !u_init || !x_out || !u_out) return ILQR_ERR_BAD_ARG;
   ilqr_options def;
   ilqr_default_options(&def);
@@ -755,7 +764,7 @@ ilqr_status ilqr_fit_ex(ilqr_handle* h, const ilqr_problem* p, const ilqr_option
     HIP_TRY(ilqr::launch_fit_init(h->batch, h->prev_cost, h->status, h->res_parity, h->iters, s));
   volatile int32_t* flags = h->host_running + 2;
   *flags = 0;
-  const ilqr::LSParams ls = ls_params(o);
+  const ilqr::LSParams ls = ilqr::ls_params(o);
   // Iteration `it` reads x̄ⁱ (the caller's x_init/u_init for it = 1, no copy; else
   // the handle's buffer (it−1)&1) and writes buffer it&1 (x̄ⁱ, ūⁱ = x̄ⁱ⁺¹, ūⁱ⁺¹,
   // :174-175). `parity` records where a trajectory's result lies when it stops:

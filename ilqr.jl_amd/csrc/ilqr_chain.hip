@@ -33,7 +33,6 @@
 #include <cstring>
 #include <string>
 #include <type_traits>
-#include <vector>
 
 #include "../../include/ilqr.h"
 #include "ilqr_internal.h"
@@ -1751,6 +1750,16 @@ __device__ unsigned chain_backward4_wave(const ChainK<V, 2>& P, int b0, int B, u
 
 constexpr int CH_WG = 64;
 
+// The chain constants go to LDS in the forward kernels: as a kernel argument they overflow
+// the SGPR file (~210 SGPRs spilled to VGPR lanes at every use). WG threads copy and meet.
+template <int WG, class PK>
+__device__ __forceinline__ void chain_consts_to_lds(PK& Ps, const PK& P) {
+  static_assert(sizeof(PK) % 4 == 0, "dword copy");
+  for (int i = threadIdx.x; i < (int)(sizeof(PK) / 4); i += WG)
+    reinterpret_cast<uint32_t*>(&Ps)[i] = reinterpret_cast<const uint32_t*>(&P)[i];
+  __syncthreads();
+}
+
 template <class V, int NJ, int NU>
 __global__ __launch_bounds__(CH_WG) void chain_backward_kernel(ChainK<V, NJ> P, int B, int T,
                                                                const V* __restrict__ x,
@@ -1792,10 +1801,8 @@ __global__ __launch_bounds__(CH_WG) void chain_forward_kernel(
     V* __restrict__ new_cost, int32_t* __restrict__ trials, int32_t* __restrict__ status,
     LSParams ls) {
   constexpr int NX = 2 * NJ;
-  __shared__ ChainK<V, NJ> Ps;  // constants in LDS (see chain_iter_forward_kernel)
-  for (int i = threadIdx.x; i < (int)(sizeof(ChainK<V, NJ>) / 4); i += CH_WG)
-    reinterpret_cast<uint32_t*>(&Ps)[i] = reinterpret_cast<const uint32_t*>(&P)[i];
-  __syncthreads();
+  __shared__ ChainK<V, NJ> Ps;
+  chain_consts_to_lds<CH_WG>(Ps, P);
   const int b = (blockIdx.x * CH_WG + threadIdx.x) / CH_FW_LANES;
   if (b >= B) return;  // the whole lane group
   const V pc = prev_cost ? prev_cost[b] : V(INFINITY);
@@ -1850,13 +1857,8 @@ __global__ __launch_bounds__(256) void chain_iter_backward4_kernel(ChainK<V, 2> 
 template <class V, int NJ, int NU>
 __global__ __launch_bounds__(CH_WG) void chain_iter_forward_kernel(ChainK<V, NJ> P, int B, int T,
                                                                    ChainIter<V> a, LSParams ls) {
-  // the chain constants go to LDS: as a kernel argument they overflow the SGPR file
-  // (~210 SGPRs spilled to VGPR lanes at every use)
   __shared__ ChainK<V, NJ> Ps;
-  static_assert(sizeof(ChainK<V, NJ>) % 4 == 0, "dword copy");
-  for (int i = threadIdx.x; i < (int)(sizeof(ChainK<V, NJ>) / 4); i += CH_WG)
-    reinterpret_cast<uint32_t*>(&Ps)[i] = reinterpret_cast<const uint32_t*>(&P)[i];
-  __syncthreads();
+  chain_consts_to_lds<CH_WG>(Ps, P);
   const int b = (blockIdx.x * CH_WG + threadIdx.x) / CH_FW_LANES;
   if (b >= B || a.status[b] != ILQR_TRAJ_OK) return;  // the whole lane group
   V du2 = V(0);
@@ -1864,19 +1866,7 @@ __global__ __launch_bounds__(CH_WG) void chain_iter_forward_kernel(ChainK<V, NJ>
   const ChainFwdOut<V> r = chain_forward_lane<V, NJ, NU, true>(Ps, b, T, a.x, a.u, a.xtraj, a.d,
                                                                a.K, pc, a.xnew, a.unew, &du2, ls);
   if ((threadIdx.x & 15) != 0) return;
-  if (a.trials) a.trials[b] = r.trials;
-  if (a.du2) a.du2[b] = du2;
-  if (a.iters) a.iters[b] = a.iter;
-  if (!r.accepted) {
-    a.status[b] = (r.cost != r.cost) ? ILQR_TRAJ_NAN : ILQR_TRAJ_LS_EXHAUSTED;
-    if (a.res_parity) a.res_parity[b] = a.parity;
-  } else {
-    a.new_cost[b] = r.cost;                // prev_cost = new_cost (:168)
-    if ((double)du2 <= ls.tol) {           // (:171) break BEFORE the update
-      a.status[b] = ILQR_TRAJ_CONVERGED;
-      if (a.res_parity) a.res_parity[b] = a.parity;
-    }
-  }
+  fwd_iter_finish(a, b, r.cost, r.accepted, r.trials, du2, ls.tol);
 }
 
 // ---------------------------------------------------------------------------
@@ -1885,9 +1875,9 @@ __global__ __launch_bounds__(CH_WG) void chain_iter_forward_kernel(ChainK<V, NJ>
 // nothing for a 16-lane group to split)
 // ---------------------------------------------------------------------------
 constexpr int CH_TRIG_SAMPLES = 15 + 18;  // M at 5 angles (3 entries), g on 3×3 (2 entries)
+constexpr double two_pi = 6.283185307179586476925286766559;  // the sample grids' (device and host)
 __global__ void chain_trig_sample_kernel(ChainK<double, 2> P, double* __restrict__ out) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  const double two_pi = 6.283185307179586476925286766559;
   const double zero[2] = {0.0, 0.0}, e0[2] = {1.0, 0.0}, e1[2] = {0.0, 1.0};
   for (int k = 0; k < 5; ++k) {  // M(q₂ = 2πk/5); M does not depend on q₁
     double c[2] = {1.0, 0.0}, sn[2] = {0.0, 0.0};
@@ -1967,19 +1957,7 @@ __global__ __launch_bounds__(64 * W) void chain_iter_forward_trig_kernel(ChainTr
   const FgOut<V> r = fwd_group<ChainTrigModel<V, NU>, L>(m, b, B, T, a.x, a.u, a.xtraj, a.d, a.K, pc, a.xnew,
                                                           a.unew, ls, a.res_parity == nullptr);
   if (!r.owner) return;
-  if (a.trials) a.trials[b] = r.trials;
-  if (a.du2) a.du2[b] = r.du2;
-  if (a.iters) a.iters[b] = a.iter;
-  if (!r.accepted) {
-    a.status[b] = (r.cost != r.cost) ? ILQR_TRAJ_NAN : ILQR_TRAJ_LS_EXHAUSTED;
-    if (a.res_parity) a.res_parity[b] = a.parity;
-  } else {
-    a.new_cost[b] = r.cost;             // prev_cost = new_cost (:168)
-    if ((double)r.du2 <= ls.tol) {      // (:171) break BEFORE the update
-      a.status[b] = ILQR_TRAJ_CONVERGED;
-      if (a.res_parity) a.res_parity[b] = a.parity;
-    }
-  }
+  fwd_iter_finish(a, b, r.cost, r.accepted, r.trials, r.du2, ls.tol);
 }
 
 // The end of a chain fit (the LQ driver's gather_kernel for V = float / double): x_out[b]
@@ -2317,40 +2295,24 @@ __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P
 
 constexpr int CH6_WG = 64;  // two trajectories per workgroup (one wave)
 
-template <int NJ>
-__device__ __forceinline__ void chain_consts_to_lds(ChainK<double, NJ>& Ps, const ChainK<double, NJ>& P) {
-  static_assert(sizeof(ChainK<double, NJ>) % 4 == 0, "dword copy");
-  for (int i = threadIdx.x; i < (int)(sizeof(ChainK<double, NJ>) / 4); i += CH6_WG)
-    reinterpret_cast<uint32_t*>(&Ps)[i] = reinterpret_cast<const uint32_t*>(&P)[i];
-  __syncthreads();
-}
-
 template <int NJ, int NU>
 __global__ __launch_bounds__(CH6_WG) void chain_forward32_kernel(
     ChainK<double, NJ> P, int B, int T, const double* __restrict__ x, const double* __restrict__ u,
     const double* __restrict__ xtraj, const double* __restrict__ d, const double* __restrict__ K,
     const double* __restrict__ prev_cost, double* __restrict__ xnew, double* __restrict__ unew,
     double* __restrict__ new_cost, int32_t* __restrict__ trials, int32_t* __restrict__ status, LSParams ls) {
-  constexpr int NX = 2 * NJ;
-  __shared__ ChainK<double, NJ> Ps;  // constants in LDS (see chain_iter_forward_kernel)
+  __shared__ ChainK<double, NJ> Ps;
   __shared__ double stage[(CH6_WG / CH6_LANES) * CH6_STAGE];
-  chain_consts_to_lds(Ps, P);
+  chain_consts_to_lds<CH6_WG>(Ps, P);
   const int b = (blockIdx.x * CH6_WG + threadIdx.x) / CH6_LANES;
   if (b >= B) return;  // the whole lane group
   const int l32 = threadIdx.x & (CH6_LANES - 1);
   const double pc = prev_cost ? prev_cost[b] : (double)INFINITY;
   const ChainFwdOut<double> r = chain_forward_group32<NJ, NU>(
       Ps, stage + (threadIdx.x / CH6_LANES) * CH6_STAGE, b, T, x, u, xtraj, d, K, pc, xnew, unew, nullptr, ls);
-  if (!r.accepted) {  // exhausted (the reference would loop forever): return the inputs
-    for (int i = l32; i < (T + 1) * NX; i += CH6_LANES)
-      xnew[(size_t)b * (T + 1) * NX + i] = x[(size_t)b * (T + 1) * NX + i];
-    for (int i = l32; i < T * NU; i += CH6_LANES) unew[(size_t)b * T * NU + i] = u[(size_t)b * T * NU + i];
-  }
-  if (l32 != 0) return;
-  new_cost[b] = r.cost;
-  if (trials) trials[b] = r.trials;
-  if (status) status[b] = r.accepted ? ILQR_TRAJ_OK
-                                     : (r.cost != r.cost ? ILQR_TRAJ_NAN : ILQR_TRAJ_LS_EXHAUSTED);
+  // every lane of the group: the 32 lanes stride the copy of an exhausted search's inputs
+  fwd_finish<2 * NJ, NU>(b, T, r.cost, r.trials, r.accepted, x, u, xnew, unew, l32, CH6_LANES, new_cost, trials,
+                         status);
 }
 
 // fit iteration, forward part. bstatus is the tiles kernel's per-trajectory result of this
@@ -2363,7 +2325,7 @@ __global__ __launch_bounds__(CH6_WG) void chain_iter_forward32_kernel(ChainK<dou
                                                                      LSParams ls) {
   __shared__ ChainK<double, NJ> Ps;
   __shared__ double stage[(CH6_WG / CH6_LANES) * CH6_STAGE];
-  chain_consts_to_lds(Ps, P);
+  chain_consts_to_lds<CH6_WG>(Ps, P);
   const int b = (blockIdx.x * CH6_WG + threadIdx.x) / CH6_LANES;
   if (b >= B || a.status[b] != ILQR_TRAJ_OK) return;  // the whole lane group
   const int l32 = threadIdx.x & (CH6_LANES - 1);
@@ -2380,19 +2342,7 @@ __global__ __launch_bounds__(CH6_WG) void chain_iter_forward32_kernel(ChainK<dou
       chain_forward_group32<NJ, NU>(Ps, stage + (threadIdx.x / CH6_LANES) * CH6_STAGE, b, T, a.x, a.u, a.xtraj,
                                     a.d, a.K, pc, a.xnew, a.unew, &du2, ls);
   if (l32 != 0) return;
-  if (a.trials) a.trials[b] = r.trials;
-  if (a.du2) a.du2[b] = du2;
-  if (a.iters) a.iters[b] = a.iter;
-  if (!r.accepted) {
-    a.status[b] = (r.cost != r.cost) ? ILQR_TRAJ_NAN : ILQR_TRAJ_LS_EXHAUSTED;
-    if (a.res_parity) a.res_parity[b] = a.parity;
-  } else {
-    a.new_cost[b] = r.cost;                // prev_cost = new_cost (:168)
-    if (du2 <= ls.tol) {                   // (:171) break BEFORE the update
-      a.status[b] = ILQR_TRAJ_CONVERGED;
-      if (a.res_parity) a.res_parity[b] = a.parity;
-    }
-  }
+  fwd_iter_finish(a, b, r.cost, r.accepted, r.trials, du2, ls.tol);
 }
 
 }  // namespace
@@ -2531,6 +2481,14 @@ ilqr::ChainTrig<V> trig_consts(const ilqr_chain_handle* h) {
   return Q;
 }
 
+using ilqr::two_pi;
+
+// weight of the sample at angle t in coefficient a of the 3-point discrete Fourier
+// transform on φ = (1, cos, sin)
+double fourier3(int a, double t) {
+  return a == 0 ? 1.0 / 3 : (a == 1 ? 2.0 / 3 * std::cos(t) : 2.0 / 3 * std::sin(t));
+}
+
 // Samples M and g with the recursion (fp64, on the device), takes their discrete
 // Fourier coefficients (exact for M's degree 2 in q₂ and g's degree 1 in each angle:
 // 5 and 3 points), and checks f against the recursion at 256 random states. Leaves
@@ -2549,7 +2507,6 @@ hipError_t chain_trig_build(ilqr_chain_handle* h) {
   if (e == hipSuccess) e = hipMemcpy(smp, dev, sizeof(smp), hipMemcpyDeviceToHost);
   if (e == hipSuccess) {
     ilqr::ChainTrig<double>& D = h->trig;
-    const double two_pi = 6.283185307179586476925286766559;
     for (int en = 0; en < 3; ++en) {  // a₀ + a₁ cos + b₁ sin + a₂ cos 2 + b₂ sin 2 from 5 samples
       double a0 = 0, a1 = 0, b1 = 0, a2 = 0, b2 = 0;
       for (int k = 0; k < 5; ++k) {
@@ -2573,8 +2530,7 @@ hipError_t chain_trig_build(ilqr_chain_handle* h) {
           for (int ka = 0; ka < 3; ++ka)
             for (int kb = 0; kb < 3; ++kb) {
               const double ta = two_pi * ka / 3.0, tb = two_pi * kb / 3.0;
-              const double fa = a == 0 ? 1.0 / 3 : (a == 1 ? 2.0 / 3 * std::cos(ta) : 2.0 / 3 * std::sin(ta));
-              const double fb = b == 0 ? 1.0 / 3 : (b == 1 ? 2.0 / 3 * std::cos(tb) : 2.0 / 3 * std::sin(tb));
+              const double fa = fourier3(a, ta), fb = fourier3(b, tb);
               acc += smp[15 + 2 * (3 * ka + kb) + i] * fa * fb;
             }
           D.Gc[i][a][b] = acc;
@@ -2619,7 +2575,6 @@ void chain_point_position(const ilqr_chain& c, int body, const double pt[3], con
 // pseudo-random angles. Returns the check's max deviation relative to the point's reach.
 double chain_task_build(const ilqr_chain& c, int body, const double pt[3], const double tgt[3],
                         double weight, bool literal, ilqr::ChainTask& C) {
-  const double two_pi = 6.283185307179586476925286766559;
   double smp[3][3][3];  // [ka][kb][coordinate]
   for (int ka = 0; ka < 3; ++ka)
     for (int kb = 0; kb < 3; ++kb) {
@@ -2634,8 +2589,7 @@ double chain_task_build(const ilqr_chain& c, int body, const double pt[3], const
         for (int ka = 0; ka < 3; ++ka)
           for (int kb = 0; kb < 3; ++kb) {
             const double ta = two_pi * ka / 3.0, tb = two_pi * kb / 3.0;
-            const double fa = a == 0 ? 1.0 / 3 : (a == 1 ? 2.0 / 3 * std::cos(ta) : 2.0 / 3 * std::sin(ta));
-            const double fb = b == 0 ? 1.0 / 3 : (b == 1 ? 2.0 / 3 * std::cos(tb) : 2.0 / 3 * std::sin(tb));
+            const double fa = fourier3(a, ta), fb = fourier3(b, tb);
             acc += smp[ka][kb][k] * fa * fb;
           }
         P[k][a][b] = acc;
@@ -2668,19 +2622,11 @@ double chain_task_build(const ilqr_chain& c, int body, const double pt[3], const
   return err / reach;
 }
 
-ilqr::LSParams chain_ls(const ilqr_options* o) {
-  ilqr_options def;
-  ilqr_default_options(&def);
-  if (!o) o = &def;
-  return ilqr::LSParams{o->mu, o->alpha0, o->shrink, o->tol, o->max_trials};
-}
-
-ilqr_status chain_check_options(const ilqr_options* o) {
-  if (!o) return ILQR_OK;
-  if (o->max_trials < 1 || o->max_iter < 0) return ILQR_ERR_BAD_ARG;
-  if (!(o->shrink > 0.0 && o->shrink < 1.0) || !(o->alpha0 > 0.0) || std::isnan(o->mu))
-    return ILQR_ERR_BAD_ARG;
-  return ILQR_OK;
+// h->lin as a compile-time constant: fn(std::integral_constant<int, LIN>{})
+template <class Fn>
+hipError_t with_lin(const ilqr_chain_handle* h, Fn&& fn) {
+  if (h->lin == ILQR_LINEARIZE_DUAL) return fn(std::integral_constant<int, ILQR_LINEARIZE_DUAL>{});
+  return fn(std::integral_constant<int, ILQR_LINEARIZE_CENTRAL_FD>{});
 }
 
 size_t vsize(const ilqr_chain_handle* h) { return h->dtype == ILQR_F32 ? 4 : 8; }
@@ -2699,23 +2645,18 @@ struct ChainOps {
     if constexpr (NJ == 2) {
       if (h->use_trig()) {
         const auto Q = trig_consts<V>(h);
-        using TK = ilqr::ChainTrig<V>;
-        if (h->lin == ILQR_LINEARIZE_DUAL)
-          ilqr::chain_linearize_kernel<V, NJ, NU, ILQR_LINEARIZE_DUAL, TK>
+        return with_lin(h, [&](auto lin) {
+          ilqr::chain_linearize_kernel<V, NJ, NU, decltype(lin)::value, ilqr::ChainTrig<V>>
               <<<grid, 256, 0, h->stream>>>(Q, h->batch, h->T, x, u, st, (V*)h->J);
-        else
-          ilqr::chain_linearize_kernel<V, NJ, NU, ILQR_LINEARIZE_CENTRAL_FD, TK>
-              <<<grid, 256, 0, h->stream>>>(Q, h->batch, h->T, x, u, st, (V*)h->J);
-        return hipGetLastError();
+          return hipGetLastError();
+        });
       }
     }
-    if (h->lin == ILQR_LINEARIZE_DUAL)
-      ilqr::chain_linearize_kernel<V, NJ, NU, ILQR_LINEARIZE_DUAL>
+    return with_lin(h, [&](auto lin) {
+      ilqr::chain_linearize_kernel<V, NJ, NU, decltype(lin)::value>
           <<<grid, 256, 0, h->stream>>>(P, h->batch, h->T, x, u, st, (V*)h->J);
-    else
-      ilqr::chain_linearize_kernel<V, NJ, NU, ILQR_LINEARIZE_CENTRAL_FD>
-          <<<grid, 256, 0, h->stream>>>(P, h->batch, h->T, x, u, st, (V*)h->J);
-    return hipGetLastError();
+      return hipGetLastError();
+    });
   }
   static hipError_t unpack(ilqr_chain_handle* h, V* A, V* Bm) {
     const size_t n = (size_t)h->batch * h->T;
@@ -2751,17 +2692,12 @@ struct ChainOps {
         if (!ilqr::fg_fits<V>(h->T)) return hipErrorInvalidValue;
         const auto Q = trig_consts<V>(h);
         const int B = h->batch;
-        const int L = ilqr::fg_lanes(B);
-        if (L == 32)
-          ilqr::chain_forward_trig_kernel<V, NU, 32, 1><<<(32 * B + 63) / 64, 64, 0, h->stream>>>(
+        return ilqr::fg_with_lanes(B, false, [&](auto g) {
+          using G = decltype(g);
+          ilqr::chain_forward_trig_kernel<V, NU, G::L, G::W><<<G::blocks(B), G::threads, 0, h->stream>>>(
               Q, B, h->T, x, u, xt, d, K, pc, xn, un, nc, tr, st, ls);
-        else if (L == 4)
-          ilqr::chain_forward_trig_kernel<V, NU, 4, 1><<<(4 * B + 63) / 64, 64, 0, h->stream>>>(
-              Q, B, h->T, x, u, xt, d, K, pc, xn, un, nc, tr, st, ls);
-        else
-          ilqr::chain_forward_trig_kernel<V, NU, 1, 4><<<(B + 255) / 256, 256, 0, h->stream>>>(
-              Q, B, h->T, x, u, xt, d, K, pc, xn, un, nc, tr, st, ls);
-        return hipGetLastError();
+          return hipGetLastError();
+        });
       }
     }
     const auto P = chain_consts<V, NJ>(h->chain);
@@ -2789,14 +2725,12 @@ struct ChainOps {
         if (!ilqr::fg_fits<V>(h->T)) return hipErrorInvalidValue;
         const auto Q = trig_consts<V>(h);
         const int B = h->batch;
-        const int L = ilqr::fg_lanes(B, a.iter >= 2);  // a fit past its first iteration
-        if (L == 32)
-          ilqr::chain_iter_forward_trig_kernel<V, NU, 32, 1><<<(32 * B + 63) / 64, 64, 0, h->stream>>>(Q, B, h->T, a, ls);
-        else if (L == 4)
-          ilqr::chain_iter_forward_trig_kernel<V, NU, 4, 1><<<(4 * B + 63) / 64, 64, 0, h->stream>>>(Q, B, h->T, a, ls);
-        else
-          ilqr::chain_iter_forward_trig_kernel<V, NU, 1, 4><<<(B + 255) / 256, 256, 0, h->stream>>>(Q, B, h->T, a, ls);
-        return hipGetLastError();
+        return ilqr::fg_with_lanes(B, a.iter >= 2, [&](auto g) {  // wide: a fit past its first iteration
+          using G = decltype(g);
+          ilqr::chain_iter_forward_trig_kernel<V, NU, G::L, G::W>
+              <<<G::blocks(B), G::threads, 0, h->stream>>>(Q, B, h->T, a, ls);
+          return hipGetLastError();
+        });
       }
     }
     const int gf = (h->batch * ilqr::CH_FW_LANES + ilqr::CH_WG - 1) / ilqr::CH_WG;
@@ -2844,30 +2778,29 @@ struct Chain6Ops {
         cost_consts(h->chain), h->batch, h->T, h->lxx, h->luu, h->lfxx);
     return hipGetLastError();
   }
-  static hipError_t linearize_to(ilqr_chain_handle* h, const V* x, const V* u, V* A, V* Bm,
-                                 const int32_t* st = nullptr) {
+  // A and B of trajectories with status OK (st null: all)
+  static hipError_t linearize(ilqr_chain_handle* h, const V* x, const V* u, const int32_t* st, V* A, V* Bm) {
     const auto P = chain_consts<V, NJ>(h->chain);
     const size_t lanes = (size_t)h->batch * h->T * (NX + NU);
     const dim3 grid((unsigned)((lanes + 255) / 256));
-    if (h->lin == ILQR_LINEARIZE_DUAL)
-      ilqr::chain_linearize_tiles_kernel<NJ, NU, ILQR_LINEARIZE_DUAL>
+    return with_lin(h, [&](auto lin) {
+      ilqr::chain_linearize_tiles_kernel<NJ, NU, decltype(lin)::value>
           <<<grid, 256, 0, h->stream>>>(P, h->batch, h->T, x, u, st, A, Bm);
-    else
-      ilqr::chain_linearize_tiles_kernel<NJ, NU, ILQR_LINEARIZE_CENTRAL_FD>
-          <<<grid, 256, 0, h->stream>>>(P, h->batch, h->T, x, u, st, A, Bm);
-    return hipGetLastError();
+      return hipGetLastError();
+    });
   }
-  // the step's tiles for trajectories with status OK (st null: all)
+  // ilqr_chain_linearize: the name its generic lambda calls on ChainOps and Chain6Ops alike
+  static hipError_t linearize_to(ilqr_chain_handle* h, const V* x, const V* u, V* A, V* Bm) {
+    return linearize(h, x, u, nullptr, A, Bm);
+  }
+  // the step's tiles, likewise
   static hipError_t tiles(ilqr_chain_handle* h, const V* x, const V* u, const int32_t* st) {
-    hipError_t e = linearize_to(h, x, u, h->tA, h->tB, st);
+    hipError_t e = linearize(h, x, u, st, h->tA, h->tB);
     if (e != hipSuccess) return e;
     const size_t n = (size_t)h->batch * (h->T + 1) * (NX + NU);
     ilqr::chain_cost_tiles_kernel<NJ, NU><<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(
         cost_consts(h->chain), h->batch, h->T, x, u, st, h->lx, h->lu, h->lfx);
     return hipGetLastError();
-  }
-  static hipError_t dynamics(ilqr_chain_handle* h, const V* x, const V* u, V* xo, int n) {
-    return ChainOps<V, NJ, NU>::dynamics(h, x, u, xo, n);
   }
   static ilqr::TileParams tile_params(const ilqr_chain_handle* h) {
     return ilqr::TileParams{h->tA, h->tB, h->lx, h->lu, h->lxx, nullptr, h->luu, h->lfx, h->lfxx};
@@ -2916,19 +2849,23 @@ bool iter_supported_dtype(int nj, int nu, int32_t dtype) {
 }
 bool handle_iterates(const ilqr_chain_handle* h) { return iter_supported_dtype(h->nj, h->nu, h->dtype); }
 
-template <class V, class Fn>
+// fn(the handle's typed operations). DYN: the call is ilqr_chain_dynamics, which every
+// dyn_supported shape answers from ChainOps in either dtype; otherwise the shapes and
+// dtypes that iterate.
+template <class V, bool DYN = false, class Fn>
 hipError_t dispatch(const ilqr_chain_handle* h, Fn&& fn) {
   if (h->nj == 2 && h->nu == 2) return fn(ChainOps<V, 2, 2>{});
   if (h->nj == 2 && h->nu == 1) return fn(ChainOps<V, 2, 1>{});
-  if constexpr (std::is_same_v<V, double>) {
-    if (h->nj == 6 && h->nu == 6) return fn(Chain6Ops{});
+  if (h->nj == 6 && h->nu == 6) {
+    if constexpr (DYN) return fn(ChainOps<V, 6, 6>{});
+    else if constexpr (std::is_same_v<V, double>) return fn(Chain6Ops{});
   }
   return hipErrorInvalidValue;
 }
-template <class Fn>
+template <bool DYN = false, class Fn>
 hipError_t dispatch_any(const ilqr_chain_handle* h, Fn&& fn) {
-  if (h->dtype == ILQR_F32) return dispatch<float>(h, fn);
-  return dispatch<double>(h, fn);
+  if (h->dtype == ILQR_F32) return dispatch<float, DYN>(h, fn);
+  return dispatch<double, DYN>(h, fn);
 }
 
 template <class V>
@@ -2951,21 +2888,6 @@ ilqr::ChainIter<V> iter_args(const ilqr_chain_handle* h, const void* x, const vo
   return a;
 }
 
-// Reduce per-trajectory status to the call status (host copy, synchronising):
-// ilqr_chain_backward / ilqr_chain_forward
-ilqr_status chain_fold_status(ilqr_chain_handle* h, const int32_t* dev_status) {
-  std::vector<int32_t> st(h->batch);
-  CH_TRY(hipMemcpyAsync(st.data(), dev_status, sizeof(int32_t) * h->batch, hipMemcpyDeviceToHost,
-                        h->stream));
-  CH_TRY(hipStreamSynchronize(h->stream));
-  bool nan = false, ls = false;
-  for (int32_t s : st) {
-    nan |= s == ILQR_TRAJ_NAN;
-    ls |= s == ILQR_TRAJ_LS_EXHAUSTED;
-  }
-  return nan ? ILQR_ERR_NAN : (ls ? ILQR_ERR_LS_EXHAUSTED : ILQR_OK);
-}
-
 template <class V>
 ilqr_status chain_fit_t(ilqr_chain_handle* h, const ilqr_options* o, const void* x_init,
                         const void* u_init, const void* x_traj, void* x_out, void* u_out,
@@ -2979,7 +2901,7 @@ ilqr_status chain_fit_t(ilqr_chain_handle* h, const ilqr_options* o, const void*
   const size_t B = (size_t)h->batch, nx = 2 * (size_t)h->nj;
   const size_t nxe = (h->T + 1) * nx, nue = (size_t)h->T * h->nu;
   hipStream_t s = h->stream;
-  const ilqr::LSParams ls = chain_ls(o);
+  const ilqr::LSParams ls = ilqr::ls_params(o);
   const int max_iter = o ? o->max_iter : 100;
   const unsigned g = (unsigned)((B + 255) / 256);
   ilqr::chain_fit_init_kernel<V><<<g, 256, 0, s>>>(h->batch, (V*)h->prev_cost, h->status, h->res_parity, h->iters);
@@ -3232,18 +3154,11 @@ ilqr_status ilqr_chain_dynamics(ilqr_chain_handle* h, const void* x, const void*
   if (!h || !x || !u || !x_next) return ILQR_ERR_BAD_ARG;
   if (n <= 0) return ILQR_ERR_BAD_DIMS;
   CH_TRY(hipSetDevice(h->device));
-  auto fn = [&](auto ops) {
+  CH_TRY(dispatch_any<true>(h, [&](auto ops) {
     using O = decltype(ops);
     using V = typename O::Value;
     return O::dynamics(h, (const V*)x, (const V*)u, (V*)x_next, n);
-  };
-  hipError_t e;
-  if (h->nj == 6) {
-    e = h->dtype == ILQR_F32 ? fn(ChainOps<float, 6, 6>{}) : fn(ChainOps<double, 6, 6>{});
-  } else {
-    e = dispatch_any(h, fn);
-  }
-  CH_TRY(e);
+  }));
   return ILQR_OK;
 }
 
@@ -3264,16 +3179,17 @@ ilqr_status ilqr_chain_backward(ilqr_chain_handle* h, const ilqr_options* o, con
                                 const void* u, void* d, void* K, int32_t* status) {
   if (!h || !x || !u || !d || !K) return ILQR_ERR_BAD_ARG;
   if (!handle_iterates(h)) return ILQR_ERR_UNSUPPORTED;
-  ilqr_status st = chain_check_options(o);
+  ilqr_status st = ilqr::check_options(o);
   if (st != ILQR_OK) return st;
   CH_TRY(hipSetDevice(h->device));
-  const double mu = chain_ls(o).mu;
+  const double mu = ilqr::ls_params(o).mu;
   CH_TRY(dispatch_any(h, [&](auto ops) {
     using O = decltype(ops);
     using V = typename O::Value;
     return O::backward(h, (const V*)x, (const V*)u, (V*)d, (V*)K, status, mu);
   }));
-  return status ? chain_fold_status(h, status) : ILQR_OK;
+  if (status) CH_TRY(ilqr::fold_status(status, h->batch, h->stream, nullptr, &st));
+  return st;
 }
 
 ilqr_status ilqr_chain_forward(ilqr_chain_handle* h, const ilqr_options* o, const void* x,
@@ -3283,17 +3199,18 @@ ilqr_status ilqr_chain_forward(ilqr_chain_handle* h, const ilqr_options* o, cons
   if (!h || !x || !u || !d || !K || !prev_cost || !x_new || !u_new || !new_cost)
     return ILQR_ERR_BAD_ARG;
   if (!handle_iterates(h)) return ILQR_ERR_UNSUPPORTED;
-  ilqr_status st = chain_check_options(o);
+  ilqr_status st = ilqr::check_options(o);
   if (st != ILQR_OK) return st;
   CH_TRY(hipSetDevice(h->device));
-  const ilqr::LSParams ls = chain_ls(o);
+  const ilqr::LSParams ls = ilqr::ls_params(o);
   CH_TRY(dispatch_any(h, [&](auto ops) {
     using O = decltype(ops);
     using V = typename O::Value;
     return O::forward(h, (const V*)x, (const V*)u, (const V*)x_traj, (const V*)d, (const V*)K,
                       (const V*)prev_cost, (V*)x_new, (V*)u_new, (V*)new_cost, trials, status, ls);
   }));
-  return status ? chain_fold_status(h, status) : ILQR_OK;
+  if (status) CH_TRY(ilqr::fold_status(status, h->batch, h->stream, nullptr, &st));
+  return st;
 }
 
 ilqr_status ilqr_chain_iterate(ilqr_chain_handle* h, const ilqr_options* o, const void* x,
@@ -3302,10 +3219,10 @@ ilqr_status ilqr_chain_iterate(ilqr_chain_handle* h, const ilqr_options* o, cons
                                int32_t* status) {
   if (!h || !x || !u || !x_new || !u_new || !new_cost || !status) return ILQR_ERR_BAD_ARG;
   if (!handle_iterates(h)) return ILQR_ERR_UNSUPPORTED;
-  ilqr_status st = chain_check_options(o);
+  ilqr_status st = ilqr::check_options(o);
   if (st != ILQR_OK) return st;
   CH_TRY(hipSetDevice(h->device));
-  const ilqr::LSParams ls = chain_ls(o);
+  const ilqr::LSParams ls = ilqr::ls_params(o);
   CH_TRY(dispatch_any(h, [&](auto ops) {
     using O = decltype(ops);
     using V = typename O::Value;
@@ -3328,7 +3245,7 @@ ilqr_status ilqr_chain_fit_ex(ilqr_chain_handle* h, const ilqr_options* o, const
   if (!h || !x_init || !u_init || !x_out || !u_out) return ILQR_ERR_BAD_ARG;
   if (hist && !hist->cost && !hist->trials && !hist->alpha && !hist->du2) hist = nullptr;
   if (!handle_iterates(h)) return ILQR_ERR_UNSUPPORTED;
-  ilqr_status st = chain_check_options(o);
+  ilqr_status st = ilqr::check_options(o);
   if (st != ILQR_OK) return st;
   CH_TRY(hipSetDevice(h->device));
   if (h->dtype == ILQR_F32)

@@ -31,7 +31,6 @@
 #include <cstdlib>
 #include <cstdint>
 #include <string>
-#include <vector>
 
 #include "../../include/ilqr.h"
 #include "ilqr_internal.h"
@@ -1551,33 +1550,6 @@ int fb_cand(int B, int T) {
   return ilqr::FB_CAND;
 }
 
-ilqr::LSParams fb_ls(const ilqr_options* o) {
-  ilqr_options def;
-  ilqr_default_options(&def);
-  if (!o) o = &def;
-  return ilqr::LSParams{o->mu, o->alpha0, o->shrink, o->tol, o->max_trials};
-}
-
-ilqr_status fb_check_options(const ilqr_options* o) {
-  if (!o) return ILQR_OK;
-  if (o->max_trials < 1 || o->max_iter < 0) return ILQR_ERR_BAD_ARG;
-  if (!(o->shrink > 0.0 && o->shrink < 1.0) || !(o->alpha0 > 0.0) || std::isnan(o->mu)) return ILQR_ERR_BAD_ARG;
-  return ILQR_OK;
-}
-
-// per-trajectory status → the call status (host copy, synchronising)
-ilqr_status fb_fold(ilqr_floating_handle* h, const int32_t* dev_status) {
-  std::vector<int32_t> st(h->batch);
-  FB_TRY(hipMemcpyAsync(st.data(), dev_status, sizeof(int32_t) * h->batch, hipMemcpyDeviceToHost, h->stream));
-  FB_TRY(hipStreamSynchronize(h->stream));
-  bool nan = false, ls = false;
-  for (int32_t s : st) {
-    nan |= s == ILQR_TRAJ_NAN;
-    ls |= s == ILQR_TRAJ_LS_EXHAUSTED;
-  }
-  return nan ? ILQR_ERR_NAN : (ls ? ILQR_ERR_LS_EXHAUSTED : ILQR_OK);
-}
-
 // fb_take_kernel over the batch: one row of blocks per trajectory, ≤ 64 blocks along it
 hipError_t fb_take(ilqr_floating_handle* h, const int32_t* move, const int32_t* fst, const int32_t* trials,
                    const double* xn, const double* un, double* x, double* u) {
@@ -1726,15 +1698,16 @@ ilqr_status ilqr_floating_linearize(ilqr_floating_handle* h, const double* x, co
 ilqr_status ilqr_floating_backward(ilqr_floating_handle* h, const ilqr_options* o, const double* x,
                                    const double* u, double* d, double* K, int32_t* status) {
   if (!h || !x || !u || !d || !K) return ILQR_ERR_BAD_ARG;
-  ilqr_status st = fb_check_options(o);
+  ilqr_status st = ilqr::check_options(o);
   if (st != ILQR_OK) return st;
   FB_TRY(hipSetDevice(h->device));
   FB_TRY(fb_linearize(h, x, u, nullptr));
   const ilqr::TileParams tp{h->A, h->Bm, h->lx, h->lu, h->lxx, nullptr, h->luu, h->lfx, h->lfxx};
   int32_t* sd = status ? status : h->bstatus;
-  FB_TRY(ilqr::launch_tiles_backward(ilqr::FB_NX, ilqr::FB_NU, tp, h->batch, h->T, d, K, sd, fb_ls(o).mu,
+  FB_TRY(ilqr::launch_tiles_backward(ilqr::FB_NX, ilqr::FB_NU, tp, h->batch, h->T, d, K, sd, ilqr::ls_params(o).mu,
                                      h->stream));
-  return fb_fold(h, sd);
+  FB_TRY(ilqr::fold_status(sd, h->batch, h->stream, nullptr, &st));
+  return st;
 }
 
 ilqr_status ilqr_floating_forward(ilqr_floating_handle* h, const ilqr_options* o, const double* x,
@@ -1742,10 +1715,10 @@ ilqr_status ilqr_floating_forward(ilqr_floating_handle* h, const ilqr_options* o
                                   const double* prev_cost, double* x_new, double* u_new, double* new_cost,
                                   int32_t* trials, int32_t* status) {
   if (!h || !x || !u || !d || !K || !prev_cost || !x_new || !u_new || !new_cost) return ILQR_ERR_BAD_ARG;
-  ilqr_status st = fb_check_options(o);
+  ilqr_status st = ilqr::check_options(o);
   if (st != ILQR_OK) return st;
   FB_TRY(hipSetDevice(h->device));
-  const ilqr::LSParams ls = fb_ls(o);
+  const ilqr::LSParams ls = ilqr::ls_params(o);
   ilqr::FbFwd fa{};
   fa.x = x;
   fa.u = u;
@@ -1769,7 +1742,8 @@ ilqr_status ilqr_floating_forward(ilqr_floating_handle* h, const ilqr_options* o
   // later accepted trial is taken from its slot; a search that accepted nothing returns
   // x, u (the closure path's rollout_forward does the same)
   FB_TRY(fb_take(h, nullptr, fa.fstatus, fa.trials, x_new, u_new, x_new, u_new));
-  return fb_fold(h, fa.fstatus);
+  FB_TRY(ilqr::fold_status(fa.fstatus, h->batch, h->stream, nullptr, &st));
+  return st;
 }
 
 ilqr_status ilqr_floating_fit(ilqr_floating_handle* h, const ilqr_options* o, const double* x_init,
@@ -1783,10 +1757,10 @@ ilqr_status ilqr_floating_fit_ex(ilqr_floating_handle* h, const ilqr_options* o,
                                  double* cost, int32_t* iters, int32_t* status, const ilqr_history* hist) {
   if (!h || !x_init || !u_init || !x_out || !u_out) return ILQR_ERR_BAD_ARG;
   if (hist && !hist->cost && !hist->trials && !hist->alpha && !hist->du2) hist = nullptr;
-  ilqr_status st = fb_check_options(o);
+  ilqr_status st = ilqr::check_options(o);
   if (st != ILQR_OK) return st;
   FB_TRY(hipSetDevice(h->device));
-  const ilqr::LSParams ls = fb_ls(o);
+  const ilqr::LSParams ls = ilqr::ls_params(o);
   const int max_iter = o ? o->max_iter : 100;
   const int B = h->batch, T = h->T;
   const size_t nxe = (size_t)(T + 1) * ilqr::FB_NX, nue = (size_t)T * ilqr::FB_NU;

@@ -275,5 +275,70 @@ inline int fg_lanes(int B, bool wide = false) {
   return B <= 65536 ? 4 : 1;
 }
 
+// fg_lanes(B, wide) as a compile-time launch shape: fn(FgLaunch<L, W>{}) for L lanes per
+// trajectory in workgroups of W waves
+template <int L_, int W_>
+struct FgLaunch {
+  static constexpr int L = L_, W = W_, threads = 64 * W_;
+  static int blocks(int B) { return (L * B + threads - 1) / threads; }
+};
+template <class Fn>
+inline hipError_t fg_with_lanes(int B, bool wide, Fn&& fn) {
+  const int L = fg_lanes(B, wide);
+  if (L == 32) return fn(FgLaunch<32, 1>{});
+  if (L == 4) return fn(FgLaunch<4, 1>{});
+  return fn(FgLaunch<1, 4>{});
+}
+
+// ---------------------------------------------------------------------------
+// The results of a forward, written once its line search has ended: fwd_iter_finish by
+// every fit-iteration forward kernel of the 2-link and chain families (whatever rolled the
+// trajectory out), fwd_finish by the six-joint standalone forward
+// ---------------------------------------------------------------------------
+
+// A standalone forward (ilqr_chain_forward) of trajectory b, called by every lane of its
+// group: an exhausted search (the reference would loop forever) returns the inputs, x_new =
+// x and u_new = u, copied by `nlanes` lanes of which this is lane `lane`; lane 0 then
+// writes the cost, the trials and the status (OK, or NAN for a NaN cost, or LS_EXHAUSTED).
+// The one-lane kernels (chain_forward_kernel, chain_forward_trig_kernel, tl_forward_kernel)
+// keep this block written out: shared, it is optimised apart from the rollout before it is
+// inlined, and the register allocation of their whole kernels moves with it.
+template <int NX, int NU, class V>
+__device__ __forceinline__ void fwd_finish(int b, int T, V cost, int ntrials, int accepted, const V* x,
+                                           const V* u, V* xnew, V* unew, int lane, int nlanes, V* new_cost,
+                                           int32_t* trials, int32_t* status) {
+  if (!accepted) {
+    for (int i = lane; i < (T + 1) * NX; i += nlanes)
+      xnew[(size_t)b * (T + 1) * NX + i] = x[(size_t)b * (T + 1) * NX + i];
+    for (int i = lane; i < T * NU; i += nlanes) unew[(size_t)b * T * NU + i] = u[(size_t)b * T * NU + i];
+  }
+  if (lane != 0) return;
+  new_cost[b] = cost;
+  if (trials) trials[b] = ntrials;
+  if (status) status[b] = accepted ? ILQR_TRAJ_OK : (cost != cost ? ILQR_TRAJ_NAN : ILQR_TRAJ_LS_EXHAUSTED);
+}
+
+// One fit iteration (forward_pass.jl:161-176) of trajectory b, from its owner lane; `a`
+// is IterArgs or ChainIter<V>. A search that accepted nothing ends the trajectory (NAN
+// for a NaN cost, else LS_EXHAUSTED) on its input iterate; an accepted one converges when
+// Σ(ū − u)² ≤ tol, and its result is then the INPUT iterate as well (res_parity).
+template <class V, class Args>
+__device__ __forceinline__ void fwd_iter_finish(const Args& a, int b, V cost, int accepted, int ntrials, V du2,
+                                                double tol) {
+  if (a.trials) a.trials[b] = ntrials;
+  if (a.du2) a.du2[b] = du2;
+  if (a.iters) a.iters[b] = a.iter;
+  if (!accepted) {
+    a.status[b] = (cost != cost) ? ILQR_TRAJ_NAN : ILQR_TRAJ_LS_EXHAUSTED;
+    if (a.res_parity) a.res_parity[b] = a.parity;
+  } else {
+    a.new_cost[b] = cost;        // prev_cost = new_cost (:168)
+    if ((double)du2 <= tol) {    // (:171) break BEFORE the update
+      a.status[b] = ILQR_TRAJ_CONVERGED;
+      if (a.res_parity) a.res_parity[b] = a.parity;
+    }
+  }
+}
+
 }  // namespace
 }  // namespace ilqr

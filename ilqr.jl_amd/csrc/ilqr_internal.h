@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/ilqr.h"
 #include "ilqr_wait.h"
 
 namespace ilqr {
@@ -25,6 +26,15 @@ struct LSParams {
   double tol;      // convergence threshold on Σ(Δu)² (forward_pass.jl:171)
   int max_trials;  // line-search cap
 };
+
+// Host helpers of every family's C ABI (defined in ilqr_abi.cpp). check_options: BAD_ARG
+// for options no search can run on (null is fine). ls_params: null means the defaults.
+ilqr_status check_options(const ilqr_options* o);
+LSParams ls_params(const ilqr_options* o);
+// Reduce a device array of n per-trajectory status words to the call status *out (host
+// copy, synchronising on s). `host`: a pinned buffer of n words, or null for a temporary.
+// A HIP failure is returned for the caller's own last-error string; *out is then unset.
+hipError_t fold_status(const int32_t* dev_status, int n, hipStream_t s, int32_t* host, ilqr_status* out);
 
 // Cooperative line search of the fused LQ iteration (lq_coop_search, ilqr_fwd_ring.h;
 // DESIGN.md §4): a trajectory still open after its first trial is published to a list,

@@ -683,8 +683,6 @@ __global__ __launch_bounds__(64 * TL_BW4_WAVES) void tl_backward_kernel(TwoLinkP
 // latency (236 vs 275 µs; profiles/r02/tl_fw_probe.log). W waves per workgroup: 1 for
 // the candidate grids (four 1-lane waves on one CU at B = 1024 ran 27.6 → 54.7 µs), 4
 // past B = 65536 (1-wave workgroups past 256 waves were packed two to a SIMD).
-inline int tl_fw_lanes(int B, bool wide = false) { return fg_lanes(B, wide); }
-
 template <int NU, int L, int W>
 __global__ __launch_bounds__(64 * W) void tl_forward_kernel(
     TwoLinkParams P, int B, int T, const double* __restrict__ x, const double* __restrict__ u,
@@ -741,19 +739,7 @@ __global__ __launch_bounds__(64 * W) void tl_iter_forward_kernel(TwoLinkParams P
   const FgOut<double> r = fwd_group<TwoLinkModel<NU>, L>(m, b, B, T, a.x, a.u, a.xtraj, a.d, a.K, pc, a.xnew,
                                                           a.unew, ls, a.res_parity == nullptr);
   if (!r.owner) return;
-  if (a.trials) a.trials[b] = r.trials;
-  if (a.du2) a.du2[b] = r.du2;
-  if (a.iters) a.iters[b] = a.iter;
-  if (!r.accepted) {
-    a.status[b] = (r.cost != r.cost) ? ILQR_TRAJ_NAN : ILQR_TRAJ_LS_EXHAUSTED;
-    if (a.res_parity) a.res_parity[b] = a.parity;
-  } else {
-    a.new_cost[b] = r.cost;  // prev_cost = new_cost (:168)
-    if (r.du2 <= ls.tol) {   // (:171) break BEFORE the update → result is the input iterate
-      a.status[b] = ILQR_TRAJ_CONVERGED;
-      if (a.res_parity) a.res_parity[b] = a.parity;
-    }
-  }
+  fwd_iter_finish(a, b, r.cost, r.accepted, r.trials, r.du2, ls.tol);
 }
 
 }  // namespace
@@ -807,17 +793,12 @@ hipError_t tl_forward_nu(const TwoLinkParams& P, int B, int T, const double* x, 
                          const double* prev_cost, double* xnew, double* unew, double* new_cost,
                          int32_t* trials, int32_t* status, const LSParams& ls, hipStream_t s) {
   if (!tl_fw_fits(T)) return hipErrorInvalidValue;
-  const int L = tl_fw_lanes(B);
-  if (L == 32)
-    tl_forward_kernel<NU, 32, 1><<<(32 * B + 63) / 64, 64, 0, s>>>(
+  return fg_with_lanes(B, false, [&](auto g) {
+    using G = decltype(g);
+    tl_forward_kernel<NU, G::L, G::W><<<G::blocks(B), G::threads, 0, s>>>(
         P, B, T, x, u, xtraj, d, K, prev_cost, xnew, unew, new_cost, trials, status, ls);
-  else if (L == 4)
-    tl_forward_kernel<NU, 4, 1><<<(4 * B + 63) / 64, 64, 0, s>>>(
-        P, B, T, x, u, xtraj, d, K, prev_cost, xnew, unew, new_cost, trials, status, ls);
-  else
-    tl_forward_kernel<NU, 1, 4><<<(B + 255) / 256, 256, 0, s>>>(
-        P, B, T, x, u, xtraj, d, K, prev_cost, xnew, unew, new_cost, trials, status, ls);
-  return hipGetLastError();
+    return hipGetLastError();
+  });
 }
 
 template <int NU>
@@ -830,14 +811,11 @@ hipError_t tl_iteration_nu(const TwoLinkParams& P, int B, int T, const IterArgs&
   const int per_wg = 4 * TL_BW4_WAVES;
   tl_iter_backward_kernel<NU><<<(B + per_wg - 1) / per_wg, 64 * TL_BW4_WAVES, 0, s>>>(P, B, T, a, J, ls.mu);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  const int L = tl_fw_lanes(B, a.iter >= 2);  // a fit past its first iteration
-  if (L == 32)
-    tl_iter_forward_kernel<NU, 32, 1><<<(32 * B + 63) / 64, 64, 0, s>>>(P, B, T, a, ls);
-  else if (L == 4)
-    tl_iter_forward_kernel<NU, 4, 1><<<(4 * B + 63) / 64, 64, 0, s>>>(P, B, T, a, ls);
-  else
-    tl_iter_forward_kernel<NU, 1, 4><<<(B + 255) / 256, 256, 0, s>>>(P, B, T, a, ls);
-  return hipGetLastError();
+  return fg_with_lanes(B, a.iter >= 2, [&](auto g) {  // wide: a fit past its first iteration
+    using G = decltype(g);
+    tl_iter_forward_kernel<NU, G::L, G::W><<<G::blocks(B), G::threads, 0, s>>>(P, B, T, a, ls);
+    return hipGetLastError();
+  });
 }
 }  // namespace
 

@@ -526,3 +526,46 @@ def test_chain_fit_equals_iterate_replay(gpu, g2, dtype, max_iter, tol, max_tria
         assert torch.equal(got[4], ref[4])
     if nan and max_iter > 0:
         assert ref[4][1].item() == _lib.TRAJ_NAN
+
+
+# -- the rare ends of the line search (tests/forward_ends.py), per forward kernel ----------
+def _ends_case(dtype, nu):
+    """B = 5, T = 7 (ragged against 4 trajectories per wave and 16 per workgroup): a
+    seeded rollout, the solver and the adapters over its API."""
+    nb, T = 5, 7
+    s = ChainSolver(rbd_2dof_problem(nu), T, nb, dtype=dtype, linearization="fd" if dtype == torch.float32 else "dual")
+    rng = np.random.default_rng(40 + nu)
+    x0 = np.concatenate([rng.uniform(-1, 1, (nb, 2)), rng.uniform(-0.5, 0.5, (nb, 2))], axis=1)
+    u = dev(rng.uniform(-0.5, 0.5, (nb, T, nu)), dtype)
+    x = s.rollout(dev(x0, dtype), u)
+
+    def forward(x, u, d, K, pc, max_trials):
+        return s.forward(x, u, d, K, pc, options=_lib.default_options(max_trials=max_trials))
+
+    def iterate(x, u, xn, un, pc, st, nc, du2, tr, xt, o):
+        s._bind()
+        s.iterate(x, u, xn, un, pc, st, nc, du2=du2, trials=tr, x_traj=xt, options=o)
+
+    def fit(x, u, xt, max_iter, tol):
+        return s.fit(x, u, max_iter=max_iter, tol=tol, x_traj=xt)
+
+    return x, u, forward, iterate, fit
+
+
+@pytest.mark.parametrize("nu", [1, 2])
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+@pytest.mark.parametrize("end", ["forward_exhausted", "forward_nan", "iterate_exhausted", "iterate_nan",
+                                 "fit_input_kept"])
+def test_chain_search_ends(gpu, dtype, nu, end):
+    """An exhausted search and a NaN cost through ilqr_chain_forward, ilqr_chain_iterate and
+    ilqr_chain_fit, on both dynamics evaluators (the 16-lane Newton-Euler kernels and the
+    closed form's candidate groups): inputs returned bit for bit, trials = max_trials,
+    LS_EXHAUSTED / NAN, and in a fit the iteration's input kept."""
+    import forward_ends as E
+    x, u, forward, iterate, fit = _ends_case(dtype, nu)
+    if end.startswith("forward"):
+        getattr(E, "check_" + end)(forward, x, u)
+    elif end.startswith("iterate"):
+        getattr(E, "check_" + end)(iterate, x, u)
+    else:
+        E.check_fit_input_kept(fit, x, u)

@@ -424,3 +424,29 @@ def test_chain6_what_stays_closed(gpu, g6g):
     s.set_dynamics("auto")
     assert s.dynamics_mode == "rnea"
     assert s.closed_form_error == 0.0   # "not used"
+
+
+# -- 12. the rare ends of the line search (tests/forward_ends.py) --------------------------
+@pytest.mark.parametrize("end", ["forward_exhausted", "forward_nan", "iterate_exhausted", "iterate_nan",
+                                 "fit_input_kept"])
+def test_chain6_search_ends(gpu, end):
+    """An exhausted search and a NaN cost through the 32-lane forward kernels, B = 3, T = 5
+    (two trajectories per wave: the last wave half empty): inputs returned bit for bit by
+    the 32 lanes' strided copy, trials = max_trials, LS_EXHAUSTED / NAN, and in a fit the
+    iteration's input kept."""
+    import forward_ends as E
+    nb, T = 3, 5
+    s = ChainSolver(rbd_6dof_problem(gravity=True), T, nb, dtype=F64)
+    rng = np.random.default_rng(46)
+    u = dev(rng.uniform(-0.5, 0.5, (nb, T, 6)))
+    x = s.rollout(dev(rbd_initial_states(nb, 6, seed0=3)), u)
+    if end.startswith("forward"):
+        getattr(E, "check_" + end)(
+            lambda x, u, d, K, pc, mt: s.forward(x, u, d, K, pc, options=_lib.default_options(max_trials=mt)), x, u)
+    elif end.startswith("iterate"):
+        def iterate(x, u, xn, un, pc, st, nc, du2, tr, xt, o):
+            s._bind()
+            s.iterate(x, u, xn, un, pc, st, nc, du2=du2, trials=tr, x_traj=xt, options=o)
+        getattr(E, "check_" + end)(iterate, x, u)
+    else:
+        E.check_fit_input_kept(lambda x, u, xt, mi, tol: s.fit(x, u, max_iter=mi, tol=tol, x_traj=xt), x, u)

@@ -422,3 +422,29 @@ def test_tl_rollout_fast_velocity_fallback(gpu):
     for b in range(64):
         ref = O.rollout(x0[b], u[b], f)
         assert rel(x[b], ref) < TOL_ROLL * 10, b
+
+
+@pytest.mark.parametrize("nu", [1, 2])
+@pytest.mark.parametrize("end", ["forward_exhausted", "forward_nan", "iterate_exhausted", "iterate_nan",
+                                 "fit_input_kept"])
+def test_tl_search_ends(gpu, nu, end):
+    """An exhausted search and a NaN cost (tests/forward_ends.py) through ilqr_forward,
+    ilqr_iterate and ilqr_fit of the 2-link family, B = 5, T = 7 (four candidates per
+    trajectory: the second wave a quarter full): inputs returned bit for bit, trials =
+    max_trials, LS_EXHAUSTED / NAN, and in a fit the iteration's input kept."""
+    import forward_ends as E
+    nb, T = 5, 7
+    s = Solver(4, nu, T, nb, kind=_lib.PROBLEM_TWO_LINK)
+    rng = np.random.default_rng(50 + nu)
+    x0 = np.concatenate([rng.uniform(-1, 1, (nb, 2)), rng.uniform(-0.5, 0.5, (nb, 2))], axis=1)
+    u = dev(rng.uniform(-0.5, 0.5, (nb, T, nu)))
+    x = s.rollout(dev(x0), u)
+    if end.startswith("forward"):
+        getattr(E, "check_" + end)(lambda x, u, d, K, pc, mt: s.forward(x, u, d, K, pc, max_trials=mt), x, u)
+    elif end.startswith("iterate"):
+        def iterate(x, u, xn, un, pc, st, nc, du2, tr, xt, o):
+            s._bind_stream()
+            s.iterate(x, u, xn, un, pc, st, du2=du2, trials=tr, x_traj=xt, options=o, new_cost=nc)
+        getattr(E, "check_" + end)(iterate, x, u)
+    else:
+        E.check_fit_input_kept(lambda x, u, xt, mi, tol: s.fit(x, u, x_traj=xt, max_iter=mi, tol=tol), x, u)
