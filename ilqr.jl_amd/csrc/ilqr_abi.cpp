@@ -76,6 +76,13 @@ struct ilqr_handle {
   // turns it off): per-trajectory records, candidate costs, the publication list and
   // its counters (zeroed here, re-armed by every launch's last wave)
   bool coop = true;
+  // gain reuse on the fused path: within one fit call the gains K and the backward's
+  // solve operands are the same in every iteration (A, B, Q, R, Qf, μ fixed), so the
+  // first iteration stores the factor of H + μI here and the later ones run the
+  // vector-only backward on it. ILQR_SCHED_FULL_BACKWARD turns it off; nullptr (not (12, 4), or
+  // the allocation failed): every iteration runs the full recursion
+  bool full_bw = false;
+  double* fac = nullptr;
   ilqr::LSCoopRec* coop_rec = nullptr;
   double* coop_cost = nullptr;
   double* coop_du2 = nullptr;
@@ -206,7 +213,9 @@ ilqr_status enqueue_iteration(ilqr_handle* h, const ilqr_problem* p, const ilqr:
       ac.coop = coop ? h->coop_dev : nullptr;
       ac.coop_ctl = coop ? h->coop_ctl : nullptr;
       ac.coop_gen = coop ? ++h->coop_gen : h->coop_gen;
-      HIP_TRY(ilqr::launch_lq_iter_fused4(P, h->batch, h->T, ac, ls, h->stream, h->fw_mfma));
+      // fit's iterations ≥ 2 reuse the gains and the factor its first one stored
+      const bool vec = a.fac && a.iter >= 2;
+      HIP_TRY(ilqr::launch_lq_iter_fused4(P, h->batch, h->T, ac, ls, h->stream, h->fw_mfma, vec));
       return ILQR_OK;
     }
     HIP_TRY(ilqr::launch_lq_iter_backward(h->nx, h->nu, P, 0, h->batch, h->T, a, ls.mu, h->stream, h->bw_wave));
@@ -271,6 +280,7 @@ ilqr_status ensure_pad(ilqr_handle* h) {
   h->pad->fw_mfma = h->fw_mfma;
   h->pad->bw_wave = h->bw_wave;
   h->pad->coop = h->coop;
+  h->pad->full_bw = h->full_bw;
   return ILQR_OK;
 }
 
@@ -464,6 +474,12 @@ ilqr_status ilqr_create(ilqr_handle** out, int device, int nx, int nu, int T, in
                            h->coop_sx,  h->coop_su,   scratch ? nsl : 0};
       e = hipMemcpy(h->coop_dev, &c, sizeof(c), hipMemcpyHostToDevice);
     }
+    // the backward's factor of H + μI of one fit's first iteration (80 B per trajectory
+    // and step, 33 MB at B = 4096, T = 100); like the scratch a speed-up, not a need
+    if (e == hipSuccess && hipMalloc(&h->fac, sizeof(double) * ilqr::lq_fac_doubles(B, T)) != hipSuccess) {
+      (void)hipGetLastError();
+      h->fac = nullptr;
+    }
     if (e == hipSuccess) e = hipDeviceSynchronize();
   }
   if (e == hipSuccess && ilqr::tl_supported(nx, nu))
@@ -520,6 +536,7 @@ ilqr_status ilqr_destroy(ilqr_handle* h) {
   (void)hipFree(h->coop_su);
   (void)hipFree(h->coop_ctl);
   (void)hipFree(h->coop_dev);
+  (void)hipFree(h->fac);
   for (int c = 0; c < 2; ++c)
     if (h->ev_poll[c]) (void)hipEventDestroy(h->ev_poll[c]);
   if (h->pad) {
@@ -546,7 +563,7 @@ ilqr_status ilqr_set_stream(ilqr_handle* h, void* s) {
 ilqr_status ilqr_set_schedule(ilqr_handle* h, int flags) {
   if (!h || (flags & ~(ILQR_SCHED_PIPELINED | ILQR_SCHED_RING_FORWARD | ILQR_SCHED_BACKWARD_WAVE |
                       ILQR_SCHED_BACKWARD_BLOCK | ILQR_SCHED_FUSED | ILQR_SCHED_FORWARD_MFMA |
-                      ILQR_SCHED_SEQUENTIAL_SEARCH)) != 0)
+                      ILQR_SCHED_SEQUENTIAL_SEARCH | ILQR_SCHED_FULL_BACKWARD)) != 0)
     return ILQR_ERR_BAD_ARG;
   // every combination check before any handle state changes
   if ((flags & ILQR_SCHED_FUSED) && (flags & (ILQR_SCHED_BACKWARD_WAVE | ILQR_SCHED_PIPELINED)))
@@ -560,6 +577,7 @@ ilqr_status ilqr_set_schedule(ilqr_handle* h, int flags) {
     t->fw_ring = (flags & ILQR_SCHED_RING_FORWARD) != 0;
     t->fw_mfma = (flags & ILQR_SCHED_FORWARD_MFMA) != 0;
     t->coop = (flags & ILQR_SCHED_SEQUENTIAL_SEARCH) == 0;
+    t->full_bw = (flags & ILQR_SCHED_FULL_BACKWARD) != 0;
     t->bw_wave = (flags & (ILQR_SCHED_BACKWARD_WAVE | ILQR_SCHED_PIPELINED)) != 0 ||
                  (!(flags & ILQR_SCHED_BACKWARD_BLOCK) && h->batch < BW4_MIN_BATCH);
   }
@@ -802,6 +820,10 @@ ilqr_status ilqr_fit_ex(ilqr_handle* h, const ilqr_problem* p, const ilqr_option
     a.parity = it == 1 ? ilqr::PARITY_INPUT : par;
     a.iter = it;
     a.init = init_in_iter && it == 1;
+    // gain reuse, decided per call: iteration 1 runs the full recursion and stores the
+    // factor, iterations ≥ 2 read it and K back (enqueue_iteration). Nothing
+    // about them outlives the call: the caller may rewrite the problem in place.
+    a.fac = init_in_iter && !h->full_bw ? h->fac : nullptr;
     return a;
   };
   if (pipe) {

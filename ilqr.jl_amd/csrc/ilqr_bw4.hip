@@ -60,6 +60,7 @@ namespace {
 constexpr int BW4_SLOTS = 4;          // trajectories per wave
 constexpr int BW4_WAVES = 4;          // waves per workgroup
 constexpr int BW4_LDS = 64 + 256;     // doubles of LDS per wave: the four H tiles, L z columns
+constexpr int BW4_FAC = BW4_SLOTS * 10;  // doubles of the factor record per wave-step (gain reuse)
 
 __device__ __forceinline__ double mf4(double a, double b, double c) {
   return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0);
@@ -95,10 +96,29 @@ __device__ __forceinline__ void buf_st(double v, __amdgpu_buffer_rsrc_t r, uint3
 // NaN (bit β): the reference's @assert !any(isnan, ...) (:353-354). A NaN in any K_t
 // or d_t reaches K_0 or d_0 (S and s carry it down the recursion; no step compares,
 // selects or clamps), so the test reads the last step's gains only.
+//
+// Gain reuse: A, B, Q, R, Qf and μ are fixed for one fit call, so the
+// matrix side of the step (Y, Z, G, H, its factor, K_t, S) is the same in every iteration
+// of the call, bit for bit; only gv, d_t and s follow the iterate. MODE:
+//  * BW4_FULL  the recursion as it always was (ilqr_backward, ilqr_iterate, a fit with
+//              ILQR_SCHED_FULL_BACKWARD);
+//  * BW4_STORE the same, and each step's factor goes to `fac`: per wave-step and slot
+//              the six entries of M = L⁻¹ below the diagonal, then the four of D⁻¹
+//              (BW4_FAC doubles a wave-step), each written by the lane that holds it;
+//  * BW4_VEC   the vector side alone: K_t comes back from K (its blocks land in the lanes
+//              that stored them), the lane's M[ρ][κ] and D⁻¹[ρ] from `fac`; the solve
+//              operands Mt, Mnd are formed from them by the full mode's own line (a
+//              select, a product and an exact MFMA transpose, off the s chain), and the
+//              same source lines then run on the same operands. Writes d only. Its
+//              inputs are prefetched BW4_PF steps ahead in registers.
+enum { BW4_FULL = 0, BW4_STORE = 1, BW4_VEC = 2 };
+constexpr int BW4_PF = 8;  // with the x/u loads and the d stores: < 64 operations in flight (vmcnt)
+template <int MODE>
 __device__ unsigned lq_backward4_wave(const LQParams& P, int b0, int B, unsigned active, int T,
                                       const double* __restrict__ x, const double* __restrict__ u,
                                       double* __restrict__ d_out, double* __restrict__ K_out,
-                                      double mu, double* lds) {
+                                      double* __restrict__ fac, double mu, double* lds) {
+  constexpr bool VEC = MODE == BW4_VEC, STORE = MODE == BW4_STORE;
   constexpr int NX = 12, NU = 4;
   b0 = __builtin_amdgcn_readfirstlane(b0);
   const int l = threadIdx.x & 63;
@@ -177,17 +197,40 @@ __device__ unsigned lq_backward4_wave(const LQParams& P, int b0, int B, unsigned
   const uint32_t DEAD = 0x80000000u;  // beyond every record count
   const uint32_t kv = live ? (uint32_t)((beta * T * NU * NX + rho * NX + kap) * 8) : DEAD;
   const uint32_t dv = (live && kap == 0) ? (uint32_t)((beta * T * NU + rho) * 8) : DEAD;
+  // the wave's factor records (BW4_STORE, BW4_VEC): lane (ρ, κ) owns entry M[ρ][κ] of its
+  // slot's ten (ρ > κ) or D⁻¹[ρ] (ρ = κ), none above the diagonal; every lane reads its
+  // row's D⁻¹[ρ] beside its own
+  const auto rF = buffer_rsrc(fac + (size_t)(b0 / BW4_SLOTS) * T * BW4_FAC, (uint32_t)(T * BW4_FAC * 8));
+  const uint32_t fv = (live && rho >= kap)
+                          ? (uint32_t)((beta * 10 + (rho > kap ? rho * (rho - 1) / 2 + kap : 6 + rho)) * 8)
+                          : DEAD;
+  const uint32_t fd = live ? (uint32_t)((beta * 10 + 6 + rho) * 8) : DEAD;
+  // vector-only mode: K_t (three blocks), M[ρ][κ], D⁻¹[ρ] of the next BW4_PF steps
+  double pf[VEC ? BW4_PF : 1][5];
+  auto prefetch = [&](double (&q)[5], int tp) {
+    tp = tp > 0 ? tp : 0;  // past step 0: step 0's again (never used)
+#pragma unroll
+    for (int J = 0; J < 3; ++J) q[J] = buf_ld(rK, kv + 32 * J, (uint32_t)(tp * NU * NX * 8));
+    q[3] = buf_ld(rF, fv, (uint32_t)(tp * BW4_FAC * 8));
+    q[4] = buf_ld(rF, fd, (uint32_t)(tp * BW4_FAC * 8));
+  };
+  if constexpr (VEC) {
+#pragma unroll
+    for (int j = 0; j < BW4_PF; ++j) prefetch(pf[j], T - 1 - j);
+  }
 
   // z_t = [x_t; u_t] (cost gradient L z, :101-106): one MFMA set gives L z for steps
   // t0 .. t0-3 (column κ = step t0-κ); each step permutes its column out.
-  double Lzq[4] = {0.0, 0.0, 0.0, 0.0}, zq[4];
-  auto load_zq = [&](int t0) {  // clamped at step 0
+  // (the vector-only mode loads a block further ahead, zqn: its step is too short to
+  // hide the load behind one block)
+  double Lzq[4] = {0.0, 0.0, 0.0, 0.0}, zq[4], zqn[4];
+  auto load_zq = [&](double (&z)[4], int t0) {  // clamped at step 0
     const int tz = t0 - kap > 0 ? t0 - kap : 0;
     const uint32_t xo = (uint32_t)(((beta * (T + 1) + tz) * NX + rho) * 8);
     const uint32_t uo = (uint32_t)(((beta * T + tz) * NU + rho) * 8);
 #pragma unroll
-    for (int K = 0; K < 3; ++K) zq[K] = buf_ld(rX, xo + 32 * K, 0);
-    zq[3] = buf_ld(rU, uo, 0);
+    for (int K = 0; K < 3; ++K) z[K] = buf_ld(rX, xo + 32 * K, 0);
+    z[3] = buf_ld(rU, uo, 0);
   };
   // L z for the four steps from t0 (column κ = step t0 − κ), from zq; then the next
   // four steps' z. Computed one step ahead of its first use, so each step's column
@@ -201,9 +244,16 @@ __device__ unsigned lq_backward4_wave(const LQParams& P, int b0, int B, unsigned
       Lzq[I] = v;
     }
     Lzq[3] = mf4(LR, zq[3], 0.0);
-    load_zq(t0 - 4);
+    if constexpr (VEC) {
+#pragma unroll
+      for (int K = 0; K < 4; ++K) zq[K] = zqn[K];
+      load_zq(zqn, t0 - 8);
+    } else {
+      load_zq(zq, t0 - 4);
+    }
   };
-  load_zq(T - 1);
+  load_zq(zq, T - 1);
+  if constexpr (VEC) load_zq(zqn, T - 5);
 
   double* Hl = lds + beta * 16;
   double Klast[4];
@@ -217,9 +267,11 @@ __device__ unsigned lq_backward4_wave(const LQParams& P, int b0, int B, unsigned
 #pragma unroll
   for (int j = 0; j < 4; ++j) lz_src[j] = ((l & ~3) | j) * 4;
   // one step of the recursion; JJ = (T − 1 − t) mod 4 (the step's column of its L z block)
-  // is static: the loop below runs the steps four at a time
+  // is static: the loop below runs the steps four at a time (vector-only: BW4_PF at a
+  // time, PS = (T − 1 − t) mod BW4_PF the step's prefetch slot)
   auto step = [&](const int t, auto jc) {
-    constexpr int JJ = decltype(jc)::value;
+    constexpr int PS = decltype(jc)::value;
+    constexpr int JJ = PS & 3;
     // this step's L z columns: the permutes issue here, their LDS latency hidden behind
     // the S·F products
     double lzp[4];
@@ -230,27 +282,29 @@ __device__ unsigned lq_backward4_wave(const LQParams& P, int b0, int B, unsigned
     // that the previous step's lane permutations produce: all 24 upper-block products
     // issue first (same summation order), so the permutes' latency hides behind them.
     double Y[3][4];
+    if constexpr (!VEC) {
 #pragma unroll
-    for (int J = 3; J >= 0; --J)
+      for (int J = 3; J >= 0; --J)
 #pragma unroll
-      for (int I = 0; I < 3; ++I) {
-        double v = 0.0;
+        for (int I = 0; I < 3; ++I) {
+          double v = 0.0;
 #pragma unroll
-        for (int K = 0; K <= I; ++K) v = mf4(S[K][I], F[K][J], v);
-        Y[I][J] = v;
-      }
-    __builtin_amdgcn_sched_barrier(0);
+          for (int K = 0; K <= I; ++K) v = mf4(S[K][I], F[K][J], v);
+          Y[I][J] = v;
+        }
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int J = 3; J >= 0; --J)
+      for (int J = 3; J >= 0; --J)
 #pragma unroll
-      for (int I = 0; I < 2; ++I)
+        for (int I = 0; I < 2; ++I)
 #pragma unroll
-        for (int K = I + 1; K < 3; ++K) Y[I][J] = mf4(S[K][I], F[K][J], Y[I][J]);
-    // H = R + Rᵀ + BᵀSB → LDS, read back whole by the slot's lanes
-    double H = LRmu;
+          for (int K = I + 1; K < 3; ++K) Y[I][J] = mf4(S[K][I], F[K][J], Y[I][J]);
+      // H = R + Rᵀ + BᵀSB → LDS, read back whole by the slot's lanes
+      double H = LRmu;
 #pragma unroll
-    for (int K = 0; K < 3; ++K) H = mf4(F[K][3], Y[K][3], H);
-    Hl[rho * 4 + kap] = H;
+      for (int K = 0; K < 3; ++K) H = mf4(F[K][3], Y[K][3], H);
+      Hl[rho * 4 + kap] = H;
+    }
 
     // gradient [lx + Aᵀs | lu + Bᵀs] (:181, :269)
     double gv[4];
@@ -263,54 +317,65 @@ __device__ unsigned lq_backward4_wave(const LQParams& P, int b0, int B, unsigned
     }
     // G = BᵀSA (lux = 0) and Qxx = lxx + AᵀSA (upper blocks)
     double G[3], Z[3][3];
+    double Mn, dsel;  // this lane's entries: Mn = M[ρ][κ], D⁻¹[ρ]
+    double Kg[4];
+    if constexpr (!VEC) {
 #pragma unroll
-    for (int J = 0; J < 3; ++J) {
-      double v = 0.0;
+      for (int J = 0; J < 3; ++J) {
+        double v = 0.0;
 #pragma unroll
-      for (int K = 0; K < 3; ++K) v = mf4(F[K][3], Y[K][J], v);
-      G[J] = v;
-    }
-#pragma unroll
-    for (int I = 0; I < 3; ++I)
-#pragma unroll
-      for (int J = I; J < 3; ++J) {
-        double v = L[I][J];
-#pragma unroll
-        for (int K = 0; K < 3; ++K) v = mf4(F[K][I], Y[K][J], v);
-        Z[I][J] = v;
+        for (int K = 0; K < 3; ++K) v = mf4(F[K][3], Y[K][J], v);
+        G[J] = v;
       }
+#pragma unroll
+      for (int I = 0; I < 3; ++I)
+#pragma unroll
+        for (int J = I; J < 3; ++J) {
+          double v = L[I][J];
+#pragma unroll
+          for (int K = 0; K < 3; ++K) v = mf4(F[K][I], Y[K][J], v);
+          Z[I][J] = v;
+        }
 
-    // (H + μI) = L D Lᵀ in every lane of the slot (feedback_parameters :207-218)
-    // (read right after the write instead — its latency behind the gradient, G and
-    // Qxx MFMAs — measured slower: 103.8 -> 105.6 us)
-    wave_lds_fence();
-    double h[4][4];
+      // (H + μI) = L D Lᵀ in every lane of the slot (feedback_parameters :207-218)
+      // (read right after the write instead — its latency behind the gradient, G and
+      // Qxx MFMAs — measured slower: 103.8 -> 105.6 us)
+      wave_lds_fence();
+      double h[4][4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+      for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int k = 0; k <= i; ++k) h[i][k] = Hl[i * 4 + k];
-    wave_lds_fence();
-    LDLT<4, 1> f;
-    f.factor<false>(h, mu);  // μ is in H already
-    // M = L⁻¹ (unit lower)
-    double Mf[4][4];
-    Mf[1][0] = -f.l[1][0];
-    Mf[2][1] = -f.l[2][1];
-    Mf[2][0] = fma(f.l[2][1], f.l[1][0], -f.l[2][0]);
-    Mf[3][2] = -f.l[3][2];
-    Mf[3][1] = fma(f.l[3][2], f.l[2][1], -f.l[3][1]);
-    Mf[3][0] = fma(-f.l[3][2], Mf[2][0], fma(-f.l[3][1], Mf[1][0], -f.l[3][0]));
-    // this lane's entries: Mn = M[ρ][κ], D⁻¹[ρ]
-    // Σ (0/1 lane mask) × entry: exact (x·1 = x, x·0 = ±0 and x ± 0 = x), so the same
-    // bits as selects, in 10 f64 ops where the selects took 18 b32 ones
-    double Mn = sel_d;
+        for (int k = 0; k <= i; ++k) h[i][k] = Hl[i * 4 + k];
+      wave_lds_fence();
+      LDLT<4, 1> f;
+      f.factor<false>(h, mu);  // μ is in H already
+      // M = L⁻¹ (unit lower)
+      double Mf[4][4];
+      Mf[1][0] = -f.l[1][0];
+      Mf[2][1] = -f.l[2][1];
+      Mf[2][0] = fma(f.l[2][1], f.l[1][0], -f.l[2][0]);
+      Mf[3][2] = -f.l[3][2];
+      Mf[3][1] = fma(f.l[3][2], f.l[2][1], -f.l[3][1]);
+      Mf[3][0] = fma(-f.l[3][2], Mf[2][0], fma(-f.l[3][1], Mf[1][0], -f.l[3][0]));
+      // Σ (0/1 lane mask) × entry: exact (x·1 = x, x·0 = ±0 and x ± 0 = x), so the same
+      // bits as selects, in 10 f64 ops where the selects took 18 b32 ones
+      Mn = sel_d;
 #pragma unroll
-    for (int i = 1; i < 4; ++i)
+      for (int i = 1; i < 4; ++i)
 #pragma unroll
-      for (int j = 0; j < i; ++j) Mn = fma(sel_m[i][j], Mf[i][j], Mn);
-    double dsel = sel_r[0] * f.dinv[0];
+        for (int j = 0; j < i; ++j) Mn = fma(sel_m[i][j], Mf[i][j], Mn);
+      dsel = sel_r[0] * f.dinv[0];
 #pragma unroll
-    for (int i = 1; i < 4; ++i) dsel = fma(sel_r[i], f.dinv[i], dsel);
+      for (int i = 1; i < 4; ++i) dsel = fma(sel_r[i], f.dinv[i], dsel);
+      if constexpr (STORE) buf_st(rho == kap ? dsel : Mn, rF, fv, (uint32_t)(t * BW4_FAC * 8));
+    } else {
+      // the stored gains and factor of this step (Mn is 1 on and 0 above the diagonal, as
+      // the mask sum leaves it); its slot then takes step t − BW4_PF's
+#pragma unroll
+      for (int J = 0; J < 3; ++J) Kg[J] = pf[PS][J];
+      Mn = rho > kap ? pf[PS][3] : Id, dsel = pf[PS][4];
+      prefetch(pf[PS], t - BW4_PF);
+    }
 
     // K_aug = −(H + μI)⁻¹ [G | g] = −(D⁻¹M)ᵀ (M [G | g]): the LDLᵀ solve's two
     // triangular sweeps as two MFMA stages. A operands: M·  wants M[κ][ρ] (the
@@ -319,34 +384,37 @@ __device__ unsigned lq_backward4_wave(const LQParams& P, int b0, int B, unsigned
     // headline's near-rank-1 H: 2e-11 against the oracle where the sweeps give 1.7e-13,
     // profiles/r01/bw4_quad.txt; a residual-checked Newton-Schulz inverse measured
     // slower, tools/ablation/bw4_newton_schulz.patch.)
-    double Kg[4];
+    // (vector-only: column 3, the d block, alone)
+    constexpr int J0 = VEC ? 3 : 0;
     const double Mt = mf4(Mn, Id, 0.0), Mnd = Mn * dsel;
 #pragma unroll
-    for (int J = 0; J < 4; ++J) Kg[J] = mf4n(Mnd, mf4(Mt, J < 3 ? G[J] : gv[3], 0.0), 0.0);
+    for (int J = J0; J < 4; ++J) Kg[J] = mf4n(Mnd, mf4(Mt, J < 3 ? G[J] : gv[3], 0.0), 0.0);
 #pragma unroll
-    for (int J = 0; J < 3; ++J) buf_st(Kg[J], rK, kv + 32 * J, (uint32_t)(t * NU * NX * 8));
+    for (int J = J0; J < 3; ++J) buf_st(Kg[J], rK, kv + 32 * J, (uint32_t)(t * NU * NX * 8));
     buf_st(Kg[3], rD, dv, (uint32_t)(t * NU * 8));
 
     // step_back (:268-270): W = (H + 2μI) K_aug = μ K_aug − [G | g],
     // [S | s] = [Qxx | lx + Aᵀs] − K_augᵀ W
     double W[4];
 #pragma unroll
-    for (int J = 0; J < 3; ++J) W[J] = fma(mu, Kg[J], -G[J]);
+    for (int J = J0; J < 3; ++J) W[J] = fma(mu, Kg[J], -G[J]);
     W[3] = fma(mu, Kg[3], -gv[3]);
 #pragma unroll
     for (int I = 0; I < 3; ++I) {
 #pragma unroll
-      for (int J = I; J < 3; ++J) S[I][J] = mf4n(Kg[I], W[J], Z[I][J]);
+      for (int J = VEC ? 3 : I; J < 3; ++J) S[I][J] = mf4n(Kg[I], W[J], Z[I][J]);
       s[I] = mf4n(Kg[I], W[3], gv[I]);
     }
-    if ((t % SYM_EVERY) == 0) {
+    if constexpr (!VEC) {
+      if ((t % SYM_EVERY) == 0) {
 #pragma unroll
-      for (int I = 0; I < 3; ++I) S[I][I] = mf4(S[I][I], Ih, 0.5 * S[I][I]);
+        for (int I = 0; I < 3; ++I) S[I][I] = mf4(S[I][I], Ih, 0.5 * S[I][I]);
+      }
+#pragma unroll
+      for (int I = 0; I < 3; ++I)
+#pragma unroll
+        for (int J = I + 1; J < 3; ++J) S[J][I] = mf4(S[I][J], Id, 0.0);
     }
-#pragma unroll
-    for (int I = 0; I < 3; ++I)
-#pragma unroll
-      for (int J = I + 1; J < 3; ++J) S[J][I] = mf4(S[I][J], Id, 0.0);
 #pragma unroll
     for (int J = 0; J < 4; ++J) Klast[J] = Kg[J];
     // the next step starts a block of four: its L z now
@@ -359,11 +427,39 @@ __device__ unsigned lq_backward4_wave(const LQParams& P, int b0, int B, unsigned
   using I2 = std::integral_constant<int, 2>;
   using I3 = std::integral_constant<int, 3>;
   int t = T - 1;
-  for (; t >= 3; t -= 4) {
-    step(t, I0{});
-    step(t - 1, I1{});
-    step(t - 2, I2{});
-    step(t - 3, I3{});
+  if constexpr (VEC) {
+    using I4 = std::integral_constant<int, 4>;
+    using I5 = std::integral_constant<int, 5>;
+    using I6 = std::integral_constant<int, 6>;
+    using I7 = std::integral_constant<int, 7>;
+    static_assert(BW4_PF == 8, "one prefetch slot per step of the unrolled loop");
+    for (; t >= 7; t -= 8) {
+      step(t, I0{});
+      step(t - 1, I1{});
+      step(t - 2, I2{});
+      step(t - 3, I3{});
+      step(t - 4, I4{});
+      step(t - 5, I5{});
+      step(t - 6, I6{});
+      step(t - 7, I7{});
+    }
+    if (t >= 3) {
+      step(t, I0{});
+      step(t - 1, I1{});
+      step(t - 2, I2{});
+      step(t - 3, I3{});
+      if (t >= 4) step(t - 4, I4{});
+      if (t >= 5) step(t - 5, I5{});
+      if (t >= 6) step(t - 6, I6{});
+      t = -1;
+    }
+  } else {
+    for (; t >= 3; t -= 4) {
+      step(t, I0{});
+      step(t - 1, I1{});
+      step(t - 2, I2{});
+      step(t - 3, I3{});
+    }
   }
   if (t >= 0) step(t, I0{});
   if (t >= 1) step(t - 1, I1{});
@@ -388,7 +484,7 @@ __global__ __launch_bounds__(256) void lq_backward4_kernel(LQParams P, int B, in
   const int w = threadIdx.x >> 6;
   const int b0 = (blockIdx.x * BW4_WAVES + w) * BW4_SLOTS;
   if (b0 >= B) return;
-  const unsigned nan = lq_backward4_wave(P, b0, B, 0xFu, T, x, u, d, K, mu, lds + w * BW4_LDS);
+  const unsigned nan = lq_backward4_wave<BW4_FULL>(P, b0, B, 0xFu, T, x, u, d, K, nullptr, mu, lds + w * BW4_LDS);
   const int l = threadIdx.x & 63;
   if (status && l < BW4_SLOTS && b0 + l < B) status[b0 + l] = ((nan >> l) & 1u) ? ILQR_TRAJ_NAN : ILQR_TRAJ_OK;
 }
@@ -406,7 +502,7 @@ __global__ __launch_bounds__(256) void lq_iter_backward4_kernel(LQParams P, int 
   for (int q = 0; q < BW4_SLOTS; ++q)
     if (b0 + q < B && a.status[b0 + q] == ILQR_TRAJ_OK) active |= 1u << q;
   if (active == 0) return;
-  const unsigned nan = lq_backward4_wave(P, b0, B, active, T, a.x, a.u, a.d, a.K, mu, lds + w * BW4_LDS) & active;
+  const unsigned nan = lq_backward4_wave<BW4_FULL>(P, b0, B, active, T, a.x, a.u, a.d, a.K, nullptr, mu, lds + w * BW4_LDS) & active;
   const int l = threadIdx.x & 63;
   if (l < BW4_SLOTS && ((nan >> l) & 1u)) {
     a.status[b0 + l] = ILQR_TRAJ_NAN;  // reference: AssertionError at backward_pass.jl:353
@@ -426,10 +522,13 @@ __global__ __launch_bounds__(256) void lq_iter_backward4_kernel(LQParams P, int 
 // dispatcher packed two of them onto one SIMD.
 constexpr int FUSED_WAVES = 4;
 constexpr int FUSED_LDS = PIPE_R * RING_SLOT + RING_LAREA;  // doubles per wave
-template <bool MF>
-__global__ __launch_bounds__(64 * FUSED_WAVES) void lq_iter_fused4_kernel(LQParams P, int B, int T,
-                                                                         IterArgs a, LSParams ls) {
-  __shared__ __attribute__((aligned(16))) double lds_all[FUSED_WAVES * FUSED_LDS];
+// BW: the backward phase's mode (lq_backward4_wave): BW4_STORE in the first iteration of a
+// fit that reuses its gains, BW4_VEC in its later ones (the gains and the factor of the
+// first, read back from a.K and a.fac), BW4_FULL otherwise. One kernel name per mode
+// (below), so a kernel trace tells them apart.
+template <bool MF, int BW>
+__device__ __forceinline__ void lq_iter_fused4(const LQParams& P, int B, int T, const IterArgs& a,
+                                               const LSParams& ls, double* lds_all) {
   static_assert(FUSED_LDS >= BW4_LDS, "backward scratch fits the ring");
   const int w = threadIdx.x >> 6;
   double* lds = lds_all + w * FUSED_LDS;
@@ -478,7 +577,7 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void lq_iter_fused4_kernel(LQPara
   // PROBE 3 is that schedule's first launch (odd waves: backward only), PROBE 4 its
   // drain launch (odd waves: forward only, even waves nothing).
   if (ILQR_FUSED_DEPHASE_PROBE == 3 && active != 0 && (w & 1)) {
-    (void)lq_backward4_wave(P, b0, B, active, T, a.x, a.u, a.d, a.K, ls.mu, lds);
+    (void)lq_backward4_wave<BW4_FULL>(P, b0, B, active, T, a.x, a.u, a.d, a.K, nullptr, ls.mu, lds);
     return;
   }
   if (ILQR_FUSED_DEPHASE_PROBE == 4) {
@@ -490,12 +589,12 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void lq_iter_fused4_kernel(LQPara
     iter_forward_wave_active<12, 4>(P, b0, B, T, ai, ls, lds, ((active >> (l >> 4)) & 1u) != 0);
     __builtin_amdgcn_s_waitcnt(0);
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    (void)lq_backward4_wave(P, b0, B, active, T, a.x, a.u, a.d, a.K, ls.mu, lds);
+    (void)lq_backward4_wave<BW4_FULL>(P, b0, B, active, T, a.x, a.u, a.d, a.K, nullptr, ls.mu, lds);
     return;
   }
 #endif
   if (active != 0) {
-    const unsigned nan = lq_backward4_wave(P, b0, B, active, T, a.x, a.u, a.d, a.K, ls.mu, lds) & active;
+    const unsigned nan = lq_backward4_wave<BW>(P, b0, B, active, T, a.x, a.u, a.d, a.K, a.fac, ls.mu, lds) & active;
     if (owner && ((nan >> q) & 1u)) {
       a.status[b0 + q] = ILQR_TRAJ_NAN;  // reference: AssertionError at backward_pass.jl:353
       if (a.res_parity) a.res_parity[b0 + q] = a.parity;
@@ -515,16 +614,37 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void lq_iter_fused4_kernel(LQPara
   if (coop) lq_coop_search<12, 4>(P, B, T, ai, ls, lds, wid, b0, own);
 }
 
+#define ILQR_FUSED4_KERNEL(NAME, BW)                                                                  \
+  template <bool MF>                                                                                  \
+  __global__ __launch_bounds__(64 * FUSED_WAVES) void NAME(LQParams P, int B, int T, IterArgs a,     \
+                                                           LSParams ls) {                             \
+    __shared__ __attribute__((aligned(16))) double lds_all[FUSED_WAVES * FUSED_LDS];                  \
+    lq_iter_fused4<MF, BW>(P, B, T, a, ls, lds_all);                                                  \
+  }
+ILQR_FUSED4_KERNEL(lq_iter_fused4_kernel, BW4_FULL)
+ILQR_FUSED4_KERNEL(lq_iter_fused4_store_kernel, BW4_STORE)
+ILQR_FUSED4_KERNEL(lq_iter_fused4_vec_kernel, BW4_VEC)
+#undef ILQR_FUSED4_KERNEL
+
 }  // namespace
 
 hipError_t launch_lq_iter_fused4(const LQParams& p, int B, int T, const IterArgs& a, const LSParams& ls,
-                                 hipStream_t s, bool mfma) {
+                                 hipStream_t s, bool mfma, bool vec) {
   if (B <= 0) return hipSuccess;
+  if (vec && (!a.fac || a.init)) return hipErrorInvalidValue;  // nothing to read back
   const int per_wg = FUSED_WAVES * BW4_SLOTS;
-  if (mfma)
-    lq_iter_fused4_kernel<true><<<(B + per_wg - 1) / per_wg, 64 * FUSED_WAVES, 0, s>>>(p, B, T, a, ls);
-  else
-    lq_iter_fused4_kernel<false><<<(B + per_wg - 1) / per_wg, 64 * FUSED_WAVES, 0, s>>>(p, B, T, a, ls);
+  const int grid = (B + per_wg - 1) / per_wg;
+  auto go = [&](auto kernel) { kernel<<<grid, 64 * FUSED_WAVES, 0, s>>>(p, B, T, a, ls); };
+  const int bw = vec ? BW4_VEC : (a.fac ? BW4_STORE : BW4_FULL);
+  if (mfma) {
+    if (bw == BW4_VEC) go(lq_iter_fused4_vec_kernel<true>);
+    else if (bw == BW4_STORE) go(lq_iter_fused4_store_kernel<true>);
+    else go(lq_iter_fused4_kernel<true>);
+  } else {
+    if (bw == BW4_VEC) go(lq_iter_fused4_vec_kernel<false>);
+    else if (bw == BW4_STORE) go(lq_iter_fused4_store_kernel<false>);
+    else go(lq_iter_fused4_kernel<false>);
+  }
   return hipGetLastError();
 }
 

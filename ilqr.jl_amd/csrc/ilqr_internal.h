@@ -83,6 +83,8 @@ struct IterArgs {
   double* unew;         // (B, T, nu)
   double* K;            // (B, T, nu, nx) gains workspace
   double* d;            // (B, T, nu)
+  double* fac;          // (ceil(B/4), T, 4, 10) the fused LQ kernel's factor of H + μI (gain reuse within
+                        // one fit: written by a full backward, read by a vector-only one); nullptr: none
   const double* prev_cost;  // (B) in; nullptr = +Inf (fit's first iteration, forward_pass.jl:159)
   double* new_cost;         // (B) out: cost of the accepted rollout (may alias prev_cost)
   double* du2;          // (B) out, may be null
@@ -114,9 +116,13 @@ hipError_t launch_lq_backward4(const LQParams& p, int B, int T, const double* x,
 hipError_t launch_lq_iter_backward4(const LQParams& p, int B, int T, const IterArgs& a, double mu,
                                     hipStream_t s);
 // backward (four trajectories per wave) + LDS-ring forward of one fit iteration in one
-// launch, (12, 4) only; the same bits as the two launches
+// launch, (12, 4) only; the same bits as the two launches. `vec`: the backward phase
+// reuses the gains in a.K and the factor in a.fac (both written by an earlier
+// launch of the same fit with the same problem and μ) and recomputes d only: the same bits
 hipError_t launch_lq_iter_fused4(const LQParams& p, int B, int T, const IterArgs& a, const LSParams& ls,
-                                 hipStream_t s, bool mfma = false);
+                                 hipStream_t s, bool mfma = false, bool vec = false);
+// doubles of IterArgs::fac for B trajectories of T steps
+inline size_t lq_fac_doubles(size_t B, size_t T) { return (B + 3) / 4 * T * 40; }
 hipError_t launch_lq_backward_v6(int nx, int nu, const LQParams& p, int B, int T, const double* x,
                                  const double* u, double* d, double* K, int32_t* status, double mu,
                                  hipStream_t s);

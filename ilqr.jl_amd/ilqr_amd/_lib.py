@@ -40,6 +40,7 @@ SCHED_BACKWARD_BLOCK = 8
 SCHED_FUSED = 16
 SCHED_FORWARD_MFMA = 32
 SCHED_SEQUENTIAL_SEARCH = 64
+SCHED_FULL_BACKWARD = 128
 MULTI_WARM_START = 1
 MULTI_USE_X_TRAJ = 2
 

@@ -107,7 +107,7 @@ class Solver:
 
     def set_schedule(self, pipelined: bool = False, ring_forward: bool = True,
                      backward: str = "auto", fused: bool = True, forward_mfma: bool = False,
-                     sequential_search: bool = False):
+                     sequential_search: bool = False, full_backward: bool = False):
         """LQ launch schedule (ilqr_set_schedule). pipelined: fit overlaps half of the
         workgroups' forward passes with the other half's backward passes (implies
         backward="wave"); ring_forward: the forward pass streams its inputs HBM → LDS
@@ -117,13 +117,16 @@ class Solver:
         "block" backward and the ring forward); forward_mfma: the ring forward's mat-vecs
         on the 4-block f64 MFMA (other rounding); sequential_search: the fused iteration's
         line search trial after trial per wave instead of the cooperative search (same
-        bits, include/ilqr.h). Schedules with the same backward kernel and forward form
-        return the same bits."""
+        bits, include/ilqr.h); full_backward: every iteration of a fit runs the full
+        backward recursion instead of reusing the first iteration's gains and factor
+        (same bits; fused path only). Schedules with the same backward kernel and forward
+        form return the same bits."""
         bk = {"auto": 0, "wave": _lib.SCHED_BACKWARD_WAVE, "block": _lib.SCHED_BACKWARD_BLOCK}[backward]
         flags = ((_lib.SCHED_PIPELINED if pipelined else 0) | (_lib.SCHED_RING_FORWARD if ring_forward else 0)
                  | bk | (_lib.SCHED_FUSED if fused and not pipelined and backward != "wave" else 0)
                  | (_lib.SCHED_FORWARD_MFMA if forward_mfma else 0)
-                 | (_lib.SCHED_SEQUENTIAL_SEARCH if sequential_search else 0))
+                 | (_lib.SCHED_SEQUENTIAL_SEARCH if sequential_search else 0)
+                 | (_lib.SCHED_FULL_BACKWARD if full_backward else 0))
         _lib.check(self.lib.ilqr_set_schedule(self.h, flags), "ilqr_set_schedule")
 
     def set_problem(self, lq):

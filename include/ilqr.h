@@ -174,8 +174,18 @@ ilqr_status ilqr_sync(ilqr_handle* h);
  *                            rollout): the same x̄, ū, cost, Σ(ū − u)², trial count and
  *                            status, bit for bit (max_trials ≤ 64, else
  *                            sequential).
- * Schedules with the same backward kernel return the same bits; the two backward
- * kernels agree to rounding. Unknown bits, or BLOCK with WAVE or
+ *   ILQR_SCHED_FULL_BACKWARD every iteration of a fit runs the full backward recursion.
+ *                            Without it (the default) a fit on the fused path runs it in
+ *                            its first iteration only: A, B, Q, R, Qf and mu are fixed
+ *                            for the call, so the gains K_t and the factor of H + mu I
+ *                            are the same in every iteration, and iterations >= 2 read
+ *                            them back and recompute only d_t and the value gradient:
+ *                            the same bits. Nothing is kept between
+ *                            calls: every fit's first iteration reads the problem
+ *                            anew. Ignored off the fused path and by ilqr_iterate /
+ *                            ilqr_backward, which always run the full recursion.
+ * Schedules with the same backward kernel return the same bits, with or without
+ * ILQR_SCHED_FULL_BACKWARD; the two backward kernels agree to rounding. Unknown bits, or BLOCK with WAVE or
  * PIPELINED → ILQR_ERR_BAD_ARG. */
 #define ILQR_SCHED_PIPELINED 1
 #define ILQR_SCHED_RING_FORWARD 2
@@ -184,6 +194,7 @@ ilqr_status ilqr_sync(ilqr_handle* h);
 #define ILQR_SCHED_FUSED 16
 #define ILQR_SCHED_FORWARD_MFMA 32
 #define ILQR_SCHED_SEQUENTIAL_SEARCH 64
+#define ILQR_SCHED_FULL_BACKWARD 128
 ilqr_status ilqr_set_schedule(ilqr_handle* h, int flags);
 
 /* iLQR.backward_pass (backward_pass.jl:324-357): gains d (batch,T,nu) and
