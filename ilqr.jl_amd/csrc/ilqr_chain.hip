@@ -23,6 +23,14 @@
 //    (fp32 or fp64). Six joints (the 6-DoF arm, fp64): the linearisation and the costs
 //    written as tiles for the wide tiles recursion (ilqr_tiles.hip) and a 32-lane
 //    forward group per trajectory — "Six-joint chains" below.
+//  * cost_functions.jl's simple_final_cost / simple_immediate_cost (src/cost_functions.jl:
+//    5-54) in place of the joint-space costs: on 2-joint chains the point's coordinates as
+//    a polynomial sampled at the call (ChainTask, ilqr_chain_set_simple_costs, closed-form
+//    dynamics only); on six joints the kinematics composed on the device at every
+//    evaluation, analytic derivatives as the terminal tiles and the task cost inside the
+//    32-lane forward group (ChainTaskK, ilqr_chain_set_task_costs,
+//    ilqr_chain_final_cost_quadratize; fp64). ilqr_chain_set_simple_costs keeps refusing
+//    six joints, and a six-joint fp32 handle answers dynamics only.
 // Layout as the other families (include/ilqr.h): x (B, T+1, nx), u/d (B, T, nu),
 // K (B, T, nu, nx), trajectory slowest, nx = 2·n_joints.
 #include <hip/hip_runtime.h>
@@ -2127,8 +2135,9 @@ __global__ __launch_bounds__(256) void chain_cost_tiles_kernel(ChainCostK<NJ> C,
 }
 
 // The Hessian tiles lxx = diag(2qw, 0), luu = diag(2rw), lfxx = diag(2qfw, 0): they depend
-// on neither the state nor the step, and the handle's cost is fixed, so they are written
-// once when the handle is created. One lane per (b, t ≤ T, element of the larger tile).
+// on neither the state nor the step, so they are written when the handle is created and
+// when its cost mode changes (a task mode: q = qf = 0, r = 1, and lfxx rewritten by every
+// backward). One lane per (b, t ≤ T, element of the larger tile).
 template <int NJ, int NU>
 __global__ __launch_bounds__(256) void chain_cost_hessians_kernel(ChainCostK<NJ> C, int B, int T,
                                                                   double* __restrict__ lxx,
@@ -2158,6 +2167,185 @@ __global__ __launch_bounds__(256) void chain_cost_hessians_kernel(ChainCostK<NJ>
   }
 }
 
+// ---------------------------------------------------------------------------
+// cost_functions.jl's task-space costs on the tiles path (ilqr_chain_set_task_costs): the
+// point's kinematics composed at every evaluation. The sampled polynomial of the 2-joint
+// closed form (ChainTask) would carry 3^NJ coefficients here.
+// ---------------------------------------------------------------------------
+struct ChainTaskK {
+  double pt[3];     // the point in body `body`'s frame
+  double t[3];      // final_target
+  double w;         // weight
+  int32_t body;     // −1 (the fixed base) .. NJ − 1
+  int32_t literal;  // the reference's reading: p_z against every target component
+};
+
+// (transform_to_root(state, body) * point).v: x_parent = p_i + R0_i·Rot(a_i, q_i)·x_child
+// from `body` down, in chain_point_position's / oracle.cost_functions.point_position's
+// operation order and without contraction, so the value differs from theirs by the
+// rounding of sin and cos only. Uniform in the lane: no lane-dependent order.
+template <int NJ>
+__device__ __forceinline__ void chain_point_fk(const ChainK<double, NJ>& P, const ChainTaskK& C,
+                                               const double (&q)[NJ], double (&p)[3]) {
+#pragma clang fp contract(off)
+  double w[3] = {C.pt[0], C.pt[1], C.pt[2]};
+#pragma unroll
+  for (int i = NJ - 1; i >= 0; --i) {
+    if (i > C.body) continue;
+    double s, c;
+    vsincos(q[i], s, c);
+    const double a0 = P.ax[i][0], a1 = P.ax[i][1], a2 = P.ax[i][2];
+    const double axw[3] = {a1 * w[2] - a2 * w[1], a2 * w[0] - a0 * w[2], a0 * w[1] - a1 * w[0]};
+    const double adw = a0 * w[0] + a1 * w[1] + a2 * w[2];
+    const double k = (1.0 - c) * adw;
+    double r[3];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) r[e] = c * w[e] + s * axw[e] + k * P.ax[i][e];
+#pragma unroll
+    for (int e = 0; e < 3; ++e)
+      w[e] = P.p[i][e] + (P.R0[i][3 * e] * r[0] + P.R0[i][3 * e + 1] * r[1] + P.R0[i][3 * e + 2] * r[2]);
+  }
+#pragma unroll
+  for (int e = 0; e < 3; ++e) p[e] = w[e];
+}
+
+// ℓ_f = weight · ((e₁² + e₂²) + e₃²), eₖ = p_k − t_k (p_z for every k in the reference's
+// reading), the oracle's summation order (cost_functions.jl:21-23)
+__device__ __forceinline__ double chain_task_value(const ChainTaskK& C, const double (&p)[3]) {
+#pragma clang fp contract(off)
+  double acc = 0.0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double e = (C.literal ? p[2] : p[k]) - C.t[k];
+    acc = acc + e * e;
+  }
+  return C.w * acc;
+}
+
+// simple_immediate_cost: Σ uᵢ², `acc + u*u` in index order (cost_functions.jl:45-51)
+template <int NU>
+__device__ __forceinline__ double chain_task_stage(const double (&u)[NU]) {
+#pragma clang fp contract(off)
+  double acc = 0.0;
+#pragma unroll
+  for (int a = 0; a < NU; ++a) acc = acc + u[a] * u[a];
+  return acc;
+}
+
+// final_cost_quadratization (backward_pass.jl:134-153) of the task cost at one state:
+// ℓ_f, ∇ℓ_f = 2w Σₖ eₖ∇pₖ and the upper triangle i ≤ j of ∇²ℓ_f = 2w Σₖ (∇pₖ∇pₖᵀ + eₖ∇²pₖ)
+// on the joint block. The derivatives are analytic in geometric form: with âᵢ, oᵢ the
+// root-frame axis and origin of joint i (one root-to-tip pass of the joint transforms),
+// ∂p/∂qᵢ = âᵢ × (p − oᵢ) and ∂²p/∂qᵢ∂qⱼ = âᵢ × ∂p/∂qⱼ for i ≤ j ≤ body, zero beyond `body`.
+template <int NJ>
+__device__ void chain_task_quad6(const ChainK<double, NJ>& P, const ChainTaskK& C, const double (&q)[NJ],
+                                 double& cost, double (&g)[NJ], double (&H)[NJ][NJ]) {
+  double p[3];
+  chain_point_fk<NJ>(P, C, q, p);
+  cost = chain_task_value(C, p);
+  double Rw[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, o[3] = {0.0, 0.0, 0.0};
+  double ah[NJ][3], J[NJ][3];
+#pragma unroll
+  for (int i = 0; i < NJ; ++i) {
+    if (i > C.body) {
+#pragma unroll
+      for (int e = 0; e < 3; ++e) ah[i][e] = J[i][e] = 0.0;
+      continue;
+    }
+    double s, c, R[9], Rn[9], on[3];
+    vsincos(q[i], s, c);
+    joint_rot(P, i, c, s, R);
+    to_parent(Rw, P.p[i], on);  // oᵢ = o_parent + R_parent pᵢ
+#pragma unroll
+    for (int e = 0; e < 3; ++e) o[e] += on[e];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        Rn[3 * r + k] = Rw[3 * r] * R[k] + Rw[3 * r + 1] * R[3 + k] + Rw[3 * r + 2] * R[6 + k];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Rw[k] = Rn[k];
+    to_parent(Rw, P.ax[i], ah[i]);  // âᵢ (the axis is fixed in the joint's own frame)
+    const double r[3] = {p[0] - o[0], p[1] - o[1], p[2] - o[2]};
+    cross3(ah[i], r, J[i]);
+  }
+  double e[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) e[k] = (C.literal ? p[2] : p[k]) - C.t[k];
+  const double w2 = 2.0 * C.w;
+#pragma unroll
+  for (int i = 0; i < NJ; ++i) {
+    double gi = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) gi += e[k] * (C.literal ? J[i][2] : J[i][k]);
+    g[i] = w2 * gi;
+#pragma unroll
+    for (int j = i; j < NJ; ++j) {
+      double d2[3];
+      cross3(ah[i], J[j], d2);  // ∂²p/∂qᵢ∂qⱼ, i ≤ j
+      double hij = 0.0;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const int m = C.literal ? 2 : k;
+        hij += J[i][m] * J[j][m] + e[k] * d2[m];
+      }
+      H[i][j] = w2 * hij;
+    }
+  }
+}
+
+// The quadratization at n states x[s·xstride .. +2NJ), one lane per state:
+//  * the terminal tiles of a task mode (xstride = (T + 1)·NX, x offset to x_N by the
+//    caller): lfx and lfxx, the latter exactly symmetric (i ≤ j computed, mirrored: the
+//    tiles recursion takes it as S_N), velocity rows and columns exactly 0; trajectories
+//    whose status is not OK are skipped like chain_cost_tiles_kernel's;
+//  * ilqr_chain_final_cost_quadratize (xstride = NX), any output null; in the joint mode
+//    (joint = 1) the handle's joint-space final cost Σ qfwᵢ(θ*ᵢ − θᵢ)² instead.
+template <int NJ>
+__global__ __launch_bounds__(64) void chain_task_quad_kernel(ChainK<double, NJ> P, ChainTaskK C, int joint, int n,
+                                                             const double* __restrict__ x, size_t xstride,
+                                                             const int32_t* __restrict__ status,
+                                                             double* __restrict__ cost, double* __restrict__ grad,
+                                                             double* __restrict__ hess) {
+  constexpr int NX = 2 * NJ;
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= n) return;
+  if (status && status[b] != ILQR_TRAJ_OK) return;
+  const double* xb = x + (size_t)b * xstride;
+  double q[NJ], c, g[NJ], H[NJ][NJ];
+#pragma unroll
+  for (int i = 0; i < NJ; ++i) q[i] = xb[i];
+  if (joint) {
+    c = 0.0;
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) {
+      const double e = P.tgt[i] - q[i];
+      c = fma(P.qfw[i] * e, e, c);
+      g[i] = -2.0 * P.qfw[i] * e;
+#pragma unroll
+      for (int j = i; j < NJ; ++j) H[i][j] = i == j ? 2.0 * P.qfw[i] : 0.0;
+    }
+  } else {
+    chain_task_quad6<NJ>(P, C, q, c, g, H);
+  }
+  if (cost) cost[b] = c;
+  if (grad) {
+    double* go = grad + (size_t)b * NX;
+#pragma unroll
+    for (int i = 0; i < NX; ++i) go[i] = i < NJ ? g[i] : 0.0;
+  }
+  if (hess) {
+    double* ho = hess + (size_t)b * NX * NX;
+#pragma unroll
+    for (int i = 0; i < NX; ++i)
+#pragma unroll
+      for (int j = 0; j < NX; ++j) {
+        const int lo = i < j ? i : j, hi = i < j ? j : i;
+        ho[i * NX + j] = hi < NJ ? H[lo][hi] : 0.0;
+      }
+  }
+}
+
 // Forward rollout + α-halving line search of a six-joint chain: chain_forward_lane's
 // arithmetic in its order, every lane of a 32-lane group carrying the same x̄, ū, cost and
 // Σδu² (the dynamics split over the group: chain_xdot_cv32).
@@ -2168,7 +2356,11 @@ __global__ __launch_bounds__(256) void chain_cost_hessians_kernel(ChainCostK<NJ>
 //  * x̄_t and ū_t are stored by lanes 0..11 and 12..17 (one coalesced store each).
 constexpr int CH6_LANES = 32;
 constexpr int CH6_STAGE = 128;  // doubles per group: 4 words per lane
-template <int NJ, int NU>
+// TASK: the costs of a task mode (ℓ = Σū², ℓ_f the task cost C of x̄_N, every lane of the
+// group evaluating it on its own copy of x̄_N by the same code: the same bits in all 32) in
+// place of the joint-space ones, chosen at compile time so that the joint-cost
+// instantiations keep their instruction streams
+template <int NJ, int NU, bool TASK = false>
 __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P, double* __restrict__ stage,
                                                      int b, int T, const double* __restrict__ x,
                                                      const double* __restrict__ u,
@@ -2176,7 +2368,8 @@ __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P
                                                      const double* __restrict__ dg,
                                                      const double* __restrict__ Kg, double prev_cost,
                                                      double* __restrict__ xnew, double* __restrict__ unew,
-                                                     double* du2_out, const LSParams& ls) {
+                                                     double* du2_out, const LSParams& ls,
+                                                     const ChainTaskK& C = ChainTaskK{}) {
   using V = double;
   constexpr int NX = 2 * NJ, NK = NU * NX;
   constexpr int O_X = NK, O_XT = O_X + NX, O_U = O_XT + NJ, O_D = O_U + NU, N_IN = O_D + NU;
@@ -2242,13 +2435,17 @@ __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P
       }
       // ℓ(x̄ₖ − x_trajₖ, ūₖ) (:187-190; RBD_helper_functions.jl:85-99 on the joints)
       V lk = V(0);
+      if constexpr (TASK) {
+        lk = chain_task_stage<NU>(ubar);  // ignores x and x_traj (cost_functions.jl:45-51)
+      } else {
 #pragma unroll
-      for (int i = 0; i < NJ; ++i) {
-        const V e = P.tgt[i] - fma(-xtw, stage[O_XT + i], xb[i]);
-        lk = fma(P.qw[i] * e, e, lk);
+        for (int i = 0; i < NJ; ++i) {
+          const V e = P.tgt[i] - fma(-xtw, stage[O_XT + i], xb[i]);
+          lk = fma(P.qw[i] * e, e, lk);
+        }
+#pragma unroll
+        for (int a = 0; a < NU; ++a) lk = fma(P.rw[a] * ubar[a], ubar[a], lk);
       }
-#pragma unroll
-      for (int a = 0; a < NU; ++a) lk = fma(P.rw[a] * ubar[a], ubar[a], lk);
       cost += lk;
       {
         V w = xb[0];
@@ -2275,10 +2472,18 @@ __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P
     }
     // final_cost(x̄_N) on the raw state (:192; RBD_helper_functions.jl:105-116)
     V lf = V(0);
+    if constexpr (TASK) {
+      V q[NJ], pw[3];
 #pragma unroll
-    for (int i = 0; i < NJ; ++i) {
-      const V e = P.tgt[i] - xb[i];
-      lf = fma(P.qfw[i] * e, e, lf);
+      for (int i = 0; i < NJ; ++i) q[i] = xb[i];
+      chain_point_fk<NJ>(P, C, q, pw);
+      lf = chain_task_value(C, pw);
+    } else {
+#pragma unroll
+      for (int i = 0; i < NJ; ++i) {
+        const V e = P.tgt[i] - xb[i];
+        lf = fma(P.qfw[i] * e, e, lf);
+      }
     }
     cost += lf;
     out.trials = trial;
@@ -2345,6 +2550,55 @@ __global__ __launch_bounds__(CH6_WG) void chain_iter_forward32_kernel(ChainK<dou
   fwd_iter_finish(a, b, r.cost, r.accepted, r.trials, du2, ls.tol);
 }
 
+// The two forward kernels in a task mode: the same bodies on the TASK instantiation of the
+// group, the task cost's constants one more kernel argument. Kernels of their own, so the
+// joint-cost kernels above are the code they were.
+template <int NJ, int NU>
+__global__ __launch_bounds__(CH6_WG) void chain_forward32_task_kernel(
+    ChainK<double, NJ> P, ChainTaskK C, int B, int T, const double* __restrict__ x, const double* __restrict__ u,
+    const double* __restrict__ xtraj, const double* __restrict__ d, const double* __restrict__ K,
+    const double* __restrict__ prev_cost, double* __restrict__ xnew, double* __restrict__ unew,
+    double* __restrict__ new_cost, int32_t* __restrict__ trials, int32_t* __restrict__ status, LSParams ls) {
+  __shared__ ChainK<double, NJ> Ps;
+  __shared__ double stage[(CH6_WG / CH6_LANES) * CH6_STAGE];
+  chain_consts_to_lds<CH6_WG>(Ps, P);
+  const int b = (blockIdx.x * CH6_WG + threadIdx.x) / CH6_LANES;
+  if (b >= B) return;  // the whole lane group
+  const int l32 = threadIdx.x & (CH6_LANES - 1);
+  const double pc = prev_cost ? prev_cost[b] : (double)INFINITY;
+  const ChainFwdOut<double> r = chain_forward_group32<NJ, NU, true>(
+      Ps, stage + (threadIdx.x / CH6_LANES) * CH6_STAGE, b, T, x, u, xtraj, d, K, pc, xnew, unew, nullptr, ls, C);
+  fwd_finish<2 * NJ, NU>(b, T, r.cost, r.trials, r.accepted, x, u, xnew, unew, l32, CH6_LANES, new_cost, trials,
+                         status);
+}
+
+template <int NJ, int NU>
+__global__ __launch_bounds__(CH6_WG) void chain_iter_forward32_task_kernel(ChainK<double, NJ> P, ChainTaskK C,
+                                                                          int B, int T, ChainIter<double> a,
+                                                                          const int32_t* __restrict__ bstatus,
+                                                                          LSParams ls) {
+  __shared__ ChainK<double, NJ> Ps;
+  __shared__ double stage[(CH6_WG / CH6_LANES) * CH6_STAGE];
+  chain_consts_to_lds<CH6_WG>(Ps, P);
+  const int b = (blockIdx.x * CH6_WG + threadIdx.x) / CH6_LANES;
+  if (b >= B || a.status[b] != ILQR_TRAJ_OK) return;  // the whole lane group
+  const int l32 = threadIdx.x & (CH6_LANES - 1);
+  if (bstatus[b] != ILQR_TRAJ_OK) {  // as chain_iter_forward32_kernel
+    if (l32 == 0) {
+      a.status[b] = ILQR_TRAJ_NAN;
+      if (a.res_parity) a.res_parity[b] = a.parity;
+    }
+    return;
+  }
+  double du2 = 0.0;
+  const double pc = a.prev_cost ? a.prev_cost[b] : (double)INFINITY;
+  const ChainFwdOut<double> r =
+      chain_forward_group32<NJ, NU, true>(Ps, stage + (threadIdx.x / CH6_LANES) * CH6_STAGE, b, T, a.x, a.u,
+                                          a.xtraj, a.d, a.K, pc, a.xnew, a.unew, &du2, ls, C);
+  if (l32 != 0) return;
+  fwd_iter_finish(a, b, r.cost, r.accepted, r.trials, du2, ls.tol);
+}
+
 }  // namespace
 }  // namespace ilqr
 
@@ -2398,6 +2652,10 @@ struct ilqr_chain_handle {
   ilqr_chain created{};
   ilqr::ChainTask* task_dev = nullptr;
   const ilqr::ChainTask* task() const { return cost_mode == ILQR_CHAIN_COST_JOINT ? nullptr : task_dev; }
+  // the same factories on the tiles path (ilqr_chain_set_task_costs): the kinematics are
+  // composed on the device, these are the kernel argument
+  ilqr::ChainTaskK task6{};
+  bool task_mode() const { return cost_mode != ILQR_CHAIN_COST_JOINT; }
 };
 
 namespace {
@@ -2771,7 +3029,9 @@ struct Chain6Ops {
     }
     return C;
   }
-  // lxx, luu, lfxx once per handle (ilqr_chain_create)
+  // lxx, luu, lfxx of the handle's cost in effect: at ilqr_chain_create and at every change
+  // of the cost mode (in a task mode h->chain carries q = 0, r = 1, qf = 0: lxx = 0,
+  // luu = 2I, and lfxx is rewritten by every backward)
   static hipError_t hessians(ilqr_chain_handle* h) {
     const size_t n = (size_t)h->batch * (h->T + 1) * NX * NX;
     ilqr::chain_cost_hessians_kernel<NJ, NU><<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(
@@ -2800,6 +3060,15 @@ struct Chain6Ops {
     const size_t n = (size_t)h->batch * (h->T + 1) * (NX + NU);
     ilqr::chain_cost_tiles_kernel<NJ, NU><<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(
         cost_consts(h->chain), h->batch, h->T, x, u, st, h->lx, h->lu, h->lfx);
+    if ((e = hipGetLastError()) != hipSuccess || !h->task_mode()) return e;
+    // a task mode: lx = 0 and lu = 2u came from the weights above; the terminal tiles from x_N
+    return quadratize(h, x + (size_t)h->T * NX, (size_t)(h->T + 1) * NX, h->batch, st, nullptr, h->lfx, h->lfxx);
+  }
+  // final_cost_quadratization of the cost in effect at n states x[s·stride .. +NX)
+  static hipError_t quadratize(ilqr_chain_handle* h, const V* x, size_t stride, int n, const int32_t* st, V* cost,
+                               V* grad, V* hess) {
+    ilqr::chain_task_quad_kernel<NJ><<<(n + 63) / 64, 64, 0, h->stream>>>(
+        chain_consts<V, NJ>(h->chain), h->task6, h->task_mode() ? 0 : 1, n, x, stride, st, cost, grad, hess);
     return hipGetLastError();
   }
   static ilqr::TileParams tile_params(const ilqr_chain_handle* h) {
@@ -2817,8 +3086,12 @@ struct Chain6Ops {
                             const ilqr::LSParams& ls) {
     const auto P = chain_consts<V, NJ>(h->chain);
     const int grid = (h->batch * ilqr::CH6_LANES + ilqr::CH6_WG - 1) / ilqr::CH6_WG;
-    ilqr::chain_forward32_kernel<NJ, NU><<<grid, ilqr::CH6_WG, 0, h->stream>>>(P, h->batch, h->T, x, u, xt, d, K,
-                                                                             pc, xn, un, nc, tr, st, ls);
+    if (h->task_mode())
+      ilqr::chain_forward32_task_kernel<NJ, NU><<<grid, ilqr::CH6_WG, 0, h->stream>>>(
+          P, h->task6, h->batch, h->T, x, u, xt, d, K, pc, xn, un, nc, tr, st, ls);
+    else
+      ilqr::chain_forward32_kernel<NJ, NU><<<grid, ilqr::CH6_WG, 0, h->stream>>>(P, h->batch, h->T, x, u, xt, d, K,
+                                                                               pc, xn, un, nc, tr, st, ls);
     return hipGetLastError();
   }
   static hipError_t iteration(ilqr_chain_handle* h, const Iter& a, const ilqr::LSParams& ls) {
@@ -2831,8 +3104,12 @@ struct Chain6Ops {
     if (e != hipSuccess) return e;
     const auto P = chain_consts<V, NJ>(h->chain);
     const int grid = (h->batch * ilqr::CH6_LANES + ilqr::CH6_WG - 1) / ilqr::CH6_WG;
-    ilqr::chain_iter_forward32_kernel<NJ, NU><<<grid, ilqr::CH6_WG, 0, h->stream>>>(P, h->batch, h->T, a,
-                                                                                  h->bstatus, ls);
+    if (h->task_mode())
+      ilqr::chain_iter_forward32_task_kernel<NJ, NU><<<grid, ilqr::CH6_WG, 0, h->stream>>>(
+          P, h->task6, h->batch, h->T, a, h->bstatus, ls);
+    else
+      ilqr::chain_iter_forward32_kernel<NJ, NU><<<grid, ilqr::CH6_WG, 0, h->stream>>>(P, h->batch, h->T, a,
+                                                                                    h->bstatus, ls);
     return hipGetLastError();
   }
 };
@@ -2959,6 +3236,24 @@ ilqr_status chain_fit_t(ilqr_chain_handle* h, const ilqr_options* o, const void*
   return (f & 1) ? ILQR_ERR_NAN : ((f & 2) ? ILQR_ERR_LS_EXHAUSTED : ILQR_OK);
 }
 
+// A six-joint handle's cost mode: the weights the per-step tiles and the forward read
+// (ℓ = Σu² in a task mode: q = 0, r = 1, qf = 0; the handle's own in the joint mode) and the
+// Hessian tiles that go with them, enqueued on the handle's stream as at creation.
+// h->task6 is set by the caller.
+ilqr_status chain6_set_cost_mode(ilqr_chain_handle* h, int32_t mode) {
+  CH_TRY(hipSetDevice(h->device));
+  h->chain = h->created;
+  if (mode != ILQR_CHAIN_COST_JOINT)
+    for (int i = 0; i < ILQR_CHAIN_MAX_JOINTS; ++i) {
+      h->chain.q_weight[i] = 0.0;
+      h->chain.r_weight[i] = 1.0;
+      h->chain.qf_weight[i] = 0.0;
+    }
+  h->cost_mode = mode;
+  CH_TRY(Chain6Ops::hessians(h));
+  return ILQR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3064,7 +3359,9 @@ ilqr_status ilqr_chain_set_dynamics(ilqr_chain_handle* h, int32_t mode) {
     return ILQR_ERR_BAD_ARG;
   if (mode == ILQR_CHAIN_DYN_CLOSED_FORM && !h->trig_ok) return ILQR_ERR_UNSUPPORTED;
   // the task-space final cost is evaluated by the closed-form forward only
-  if (mode == ILQR_CHAIN_DYN_RNEA && h->cost_mode != ILQR_CHAIN_COST_JOINT) return ILQR_ERR_UNSUPPORTED;
+  // (2-joint chains; six joints compose the kinematics beside the recursion)
+  if (mode == ILQR_CHAIN_DYN_RNEA && h->cost_mode != ILQR_CHAIN_COST_JOINT && iter_supported(h->nj, h->nu))
+    return ILQR_ERR_UNSUPPORTED;
   h->dyn_mode = mode;
   return ILQR_OK;
 }
@@ -3078,6 +3375,7 @@ ilqr_status ilqr_chain_set_simple_costs(ilqr_chain_handle* h, int32_t mode, int3
     return ILQR_ERR_BAD_ARG;
   if (mode == ILQR_CHAIN_COST_JOINT) {  // the joint-space costs the handle was created with
     if (h->cost_mode != ILQR_CHAIN_COST_JOINT) {
+      if (h->nj == 6) return chain6_set_cost_mode(h, ILQR_CHAIN_COST_JOINT);  // its tiles too
       CH_TRY(hipStreamSynchronize(h->stream));  // launches in flight still read the old cost
       h->chain = h->created;
       h->cost_mode = ILQR_CHAIN_COST_JOINT;
@@ -3112,6 +3410,45 @@ ilqr_status ilqr_chain_set_simple_costs(ilqr_chain_handle* h, int32_t mode, int3
     h->chain.qf_weight[i] = 0.0;
   }
   h->cost_mode = mode;
+  return ILQR_OK;
+}
+
+ilqr_status ilqr_chain_set_task_costs(ilqr_chain_handle* h, int32_t mode, int32_t body, const double* point,
+                                      const double* final_target, double weight) {
+  if (!h) return ILQR_ERR_BAD_ARG;
+  // 2-joint chains: the sampled closed form, with its returns
+  if (iter_supported(h->nj, h->nu)) return ilqr_chain_set_simple_costs(h, mode, body, point, final_target, weight);
+  if (mode != ILQR_CHAIN_COST_JOINT && mode != ILQR_CHAIN_COST_SIMPLE &&
+      mode != ILQR_CHAIN_COST_SIMPLE_EUCLIDEAN)
+    return ILQR_ERR_BAD_ARG;
+  if (mode == ILQR_CHAIN_COST_JOINT)
+    return h->cost_mode == ILQR_CHAIN_COST_JOINT ? ILQR_OK : chain6_set_cost_mode(h, ILQR_CHAIN_COST_JOINT);
+  if (!point || !final_target || !std::isfinite(weight)) return ILQR_ERR_BAD_ARG;
+  if (body < -1 || body >= h->nj) return ILQR_ERR_BAD_ARG;
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(point[k]) || !std::isfinite(final_target[k])) return ILQR_ERR_BAD_ARG;
+  if (h->nj != 6 || !handle_iterates(h)) {
+    g_chain_error = "ilqr_chain_set_task_costs: needs a handle that iterates on the tiles path (six joints, fp64)";
+    return ILQR_ERR_UNSUPPORTED;
+  }
+  for (int k = 0; k < 3; ++k) {
+    h->task6.pt[k] = point[k];
+    h->task6.t[k] = final_target[k];
+  }
+  h->task6.w = weight;
+  h->task6.body = body;
+  h->task6.literal = mode == ILQR_CHAIN_COST_SIMPLE ? 1 : 0;
+  return chain6_set_cost_mode(h, mode);
+}
+
+ilqr_status ilqr_chain_final_cost_quadratize(ilqr_chain_handle* h, const void* x, int n, void* cost, void* grad,
+                                             void* hess) {
+  if (!h || !x) return ILQR_ERR_BAD_ARG;
+  if (n <= 0) return ILQR_ERR_BAD_DIMS;
+  if (h->nj != 6 || !handle_iterates(h)) return ILQR_ERR_UNSUPPORTED;
+  CH_TRY(hipSetDevice(h->device));
+  CH_TRY(Chain6Ops::quadratize(h, (const double*)x, Chain6Ops::NX, n, nullptr, (double*)cost, (double*)grad,
+                               (double*)hess));
   return ILQR_OK;
 }
 

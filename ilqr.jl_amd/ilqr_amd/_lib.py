@@ -163,6 +163,9 @@ SIGNATURES = {
     "ilqr_chain_closed_form_error": (C.c_double, [P]),
     "ilqr_chain_set_simple_costs": (C.c_int, [P, C.c_int32, C.c_int32, C.POINTER(C.c_double),
                                               C.POINTER(C.c_double), C.c_double]),
+    "ilqr_chain_set_task_costs": (C.c_int, [P, C.c_int32, C.c_int32, C.POINTER(C.c_double),
+                                            C.POINTER(C.c_double), C.c_double]),
+    "ilqr_chain_final_cost_quadratize": (C.c_int, [P, P, C.c_int, P, P, P]),
     "ilqr_chain_get_cost_mode": (C.c_int32, [P]),
     "ilqr_chain_sync": (C.c_int, [P]),
     "ilqr_chain_dynamics": (C.c_int, [P, P, P, P, C.c_int]),

@@ -202,18 +202,46 @@ class ChainSolver:
         problem's joint-space costs (ilqr_chain_set_simple_costs): ℓ = Σ uᵢ² and
         ℓ_f = weight·Σₖ (p_z − final_targetₖ)² for the point `point` of body `body`
         (0-based link index or the name of the joint that moves it; −1 = the base), or
-        the squared distance Σₖ (pₖ − final_targetₖ)² with euclidean=True."""
+        the squared distance Σₖ (pₖ − final_targetₖ)² with euclidean=True. A 2-joint
+        chain samples the point's closed form at this call; six joints (fp64) compose the
+        kinematics on the device at every evaluation (ilqr_chain_set_task_costs)."""
         b = body_index(self.p.chain, body)
         pt = (C.c_double * 3)(*[float(v) for v in np.asarray(point, float).reshape(3)])
         tg = (C.c_double * 3)(*[float(v) for v in np.asarray(final_target, float).reshape(3)])
         mode = _lib.CHAIN_COST_SIMPLE_EUCLIDEAN if euclidean else _lib.CHAIN_COST_SIMPLE
-        _lib.check(self.lib.ilqr_chain_set_simple_costs(self.h, mode, b, pt, tg, float(weight)),
-                   "ilqr_chain_set_simple_costs")
+        fn, name = self._cost_entry()
+        self._bind()   # the new mode's tiles are enqueued on the handle's stream
+        _lib.check(fn(self.h, mode, b, pt, tg, float(weight)), name)
+
+    def _cost_entry(self):
+        """The cost-mode entry of this handle: the sampled closed form's for the 2-joint
+        family, the on-device kinematics' for the rest."""
+        if self.lib.ilqr_chain_supported(self.nj, self.nu):
+            return self.lib.ilqr_chain_set_simple_costs, "ilqr_chain_set_simple_costs"
+        return self.lib.ilqr_chain_set_task_costs, "ilqr_chain_set_task_costs"
 
     def set_joint_costs(self):
         """Back to the ChainProblem's joint-space costs."""
-        _lib.check(self.lib.ilqr_chain_set_simple_costs(self.h, _lib.CHAIN_COST_JOINT, 0, None, None, 0.0),
-                   "ilqr_chain_set_simple_costs")
+        fn, name = self._cost_entry()
+        self._bind()
+        _lib.check(fn(self.h, _lib.CHAIN_COST_JOINT, 0, None, None, 0.0), name)
+
+    clear_simple_costs = set_joint_costs
+
+    def final_cost_quadratization(self, x):
+        """final_cost_quadratization (backward_pass.jl:134-153) of the cost in effect at the
+        states x (n, nx): (ℓ_f (n,), ∇ℓ_f (n, nx), ∇²ℓ_f (n, nx, nx)) on the device
+        (ilqr_chain_final_cost_quadratize: six joints, fp64)."""
+        n = x.shape[0]
+        _req(x, torch.float64, (n, self.nx), "x")
+        cost = self._new(n, dtype=torch.float64)
+        grad = self._new(n, self.nx, dtype=torch.float64)
+        hess = self._new(n, self.nx, self.nx, dtype=torch.float64)
+        self._bind()
+        _lib.check(self.lib.ilqr_chain_final_cost_quadratize(self.h, _ptr(x), n, _ptr(cost), _ptr(grad),
+                                                             _ptr(hess)),
+                   "ilqr_chain_final_cost_quadratize")
+        return cost, grad, hess
 
     @property
     def cost_mode(self) -> str:

@@ -17,11 +17,12 @@ unused, and both factories keep `@assert 3 == length(final_target)` (:12, :41).
 
 The mechanism is a chain of this package (ilqr_amd.urdf.Chain, a ChainProblem or a
 robot name for load_robot); `body` is the index of the link joint `body` moves (or that
-joint's name; −1 = the fixed base). With ChainDynamics on a 2-joint chain both callables
-are recognised by ilqr_amd.fit / backward_pass / forward_pass, which then solve on the
-device with ilqr_chain_set_simple_costs (the task cost's coefficients are sampled once
-per handle; no host evaluation inside the iteration). Called directly they evaluate on
-the host (one state: the reference's closure semantics).
+joint's name; −1 = the fixed base). With ChainDynamics both callables are recognised by
+ilqr_amd.fit / backward_pass / forward_pass, which then solve on the device: a 2-joint
+chain with ilqr_chain_set_simple_costs (the task cost's coefficients are sampled once per
+handle), the 6-DoF arm (float64) with ilqr_chain_set_task_costs (the kinematics composed on
+the device at every evaluation); no host evaluation inside the iteration either way. Called
+directly they evaluate on the host (one state: the reference's closure semantics).
 """
 from __future__ import annotations
 

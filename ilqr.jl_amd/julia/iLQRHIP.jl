@@ -885,10 +885,19 @@ function ChainSolver(c::Chain, nx::Integer, nu::Integer, T::Integer, nb::Integer
               "ilqr_chain_set_dynamics")
         if costs !== nothing
             mode = costs.euclidean ? ILQR_CHAIN_COST_SIMPLE_EUCLIDEAN : ILQR_CHAIN_COST_SIMPLE
-            check(ccall((:ilqr_chain_set_simple_costs, libilqr), Cint,
-                        (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Float64),
-                        r[], mode, costs.body, collect(costs.point), collect(costs.final_target), costs.weight),
-                  "ilqr_chain_set_simple_costs")
+            # by handle: the sampled closed form of the 2-joint family, or the kinematics composed
+            # on the device (six joints, fp64); the same argument list either way
+            if ccall((:ilqr_chain_supported, libilqr), Cint, (Cint, Cint), c.n_joints, c.nu) == 1
+                check(ccall((:ilqr_chain_set_simple_costs, libilqr), Cint,
+                            (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Float64),
+                            r[], mode, costs.body, collect(costs.point), collect(costs.final_target), costs.weight),
+                      "ilqr_chain_set_simple_costs")
+            else
+                check(ccall((:ilqr_chain_set_task_costs, libilqr), Cint,
+                            (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Float64),
+                            r[], mode, costs.body, collect(costs.point), collect(costs.final_target), costs.weight),
+                      "ilqr_chain_set_task_costs")
+            end
         end
     catch
         destroy(); rethrow()
@@ -917,7 +926,8 @@ Array{Float32,3} (fp32, BASELINE config 5) or Array{Float64,3}: the element type
 the device precision, as the reference's generic Julia code would. `dynamics` picks the
 2-joint evaluator (AUTO: the closed form sampled from the Newton-Euler recursion at
 creation; RNEA: the recursion itself). `costs = simple_costs(…)` replaces the chain's
-joint-space costs with cost_functions.jl's pair (2-joint chains, closed form). Nothing here
+joint-space costs with cost_functions.jl's pair (2-joint chains: the closed form,
+ilqr_chain_set_simple_costs; six joints in fp64: ilqr_chain_set_task_costs). Nothing here
 depends on the joint count: the 6-DoF arm (n_joints = nu = 6) iterates in fp64
 (ilqr_chain_supported_dtype(6, 6, ILQR_F64) == 1), so it takes Array{Float64,3}; with
 Array{Float32,3} ilqr_chain_fit returns ILQR_ERR_UNSUPPORTED. The handle

@@ -310,7 +310,9 @@ ilqr_status ilqr_fit_ex(ilqr_handle* h, const ilqr_problem* p, const ilqr_option
  * 2-joint family. A six-joint ILQR_F32 handle answers ilqr_chain_dynamics only (the rest
  * returns ILQR_ERR_UNSUPPORTED); (6, 1) is not compiled. Six joints run the recursive
  * Newton-Euler only: ilqr_chain_set_simple_costs and ilqr_chain_set_dynamics(CLOSED_FORM)
- * return ILQR_ERR_UNSUPPORTED, AUTO and RNEA both mean the recursion.
+ * return ILQR_ERR_UNSUPPORTED, AUTO and RNEA both mean the recursion. The task-space costs
+ * of cost_functions.jl on six joints are ilqr_chain_set_task_costs (kinematics composed on
+ * the device, fp64).
  * Device memory taken at creation, per (trajectory, step): a 2-joint handle keeps one
  * linearisation record (nx(nx + nu) + nx + nu words), a six-joint fp64 handle the tiles
  * of the wide Riccati kernel instead — A 144, B 72, lxx 144, luu 36, lx 12, lu 6 doubles —
@@ -394,6 +396,28 @@ typedef enum {
 ilqr_status ilqr_chain_set_simple_costs(ilqr_chain_handle* h, int32_t mode, int32_t body,
                                         const double* point, const double* final_target,
                                         double weight);
+/* cost_functions.jl's factories with the point's kinematics composed on the device at
+ * every evaluation (no sampled closed form): any handle that iterates on the tiles path
+ * (six joints, fp64). mode / body / point / final_target / weight as
+ * ilqr_chain_set_simple_costs; ILQR_CHAIN_COST_JOINT restores the handle's joint costs.
+ * The Hessian tiles of the new mode are enqueued on the handle's stream. On a 2-joint
+ * handle the call forwards to ilqr_chain_set_simple_costs (its returns, its closed-form
+ * requirement), so one name serves every handle; a handle that does not iterate (six
+ * joints, ILQR_F32) returns ILQR_ERR_UNSUPPORTED; a body outside −1..n_joints−1, a NULL or
+ * non-finite point / final_target / weight return ILQR_ERR_BAD_ARG and leave the mode as
+ * it was. ilqr_chain_set_dynamics(RNEA / AUTO) stays accepted on six joints while a task
+ * cost is set. ilqr_chain_set_simple_costs itself keeps refusing a task mode on six
+ * joints (it is the sampled closed form). */
+ilqr_status ilqr_chain_set_task_costs(ilqr_chain_handle* h, int32_t mode, int32_t body,
+                                      const double* point, const double* final_target,
+                                      double weight);
+/* final_cost_quadratization (backward_pass.jl:134-153) of the handle's cost in effect at
+ * n states: cost (n), grad (n, nx), hess (n, nx, nx); any of the three may be NULL.
+ * x (n, nx), fp64, device memory; enqueued on the handle's stream. Six-joint ILQR_F64
+ * handles (ILQR_ERR_UNSUPPORTED elsewhere). hess is exactly symmetric and its velocity
+ * rows and columns are exactly 0. */
+ilqr_status ilqr_chain_final_cost_quadratize(ilqr_chain_handle* h, const void* x, int n,
+                                             void* cost, void* grad, void* hess);
 /* the cost mode in effect, −1 for a NULL handle */
 int32_t ilqr_chain_get_cost_mode(const ilqr_chain_handle* h);
 ilqr_status ilqr_chain_sync(ilqr_chain_handle* h);

@@ -27,6 +27,8 @@ from ilqr_amd import _lib  # noqa: E402
 from ilqr_amd.chain import ChainSolver, rbd_2dof_problem, rbd_6dof_problem, rbd_initial_states  # noqa: E402
 from tools import flops as FL  # noqa: E402
 
+# --simple-cost: the task cost of tests/golden/chain6task_euc_t30 (six joints)
+SIMPLE_COST = {"point": [0.05, 0.02, 0.1], "final_target": [3.9, 3.5, 1.3], "weight": 2e3}
 PEAK_TFLOPS = {"f32": 157.3, "f64": 78.6}   # MI355X vector FP32 / FP64 (spec; MI355X_MICROARCH.md)
 
 
@@ -64,7 +66,7 @@ def cpu_baseline(pr, x, u, budget_s):
 
 
 def measure(lin="fd", B=2048, T=100, nu=1, dtype="f32", steps=100, warmup=100, device=0,
-            dynamics="auto", cpu_budget=None, base=None, problem=None):
+            dynamics="auto", cpu_budget=None, base=None, problem=None, simple_cost=False):
     """Config 5's fit-iteration rate and per-kernel roofline for one linearisation (one
     dict; bench.py's secondary_configs calls this after its headline, outside the
     headline's timed region)."""
@@ -76,6 +78,9 @@ def measure(lin="fd", B=2048, T=100, nu=1, dtype="f32", steps=100, warmup=100, d
     x0 = rbd_initial_states(B, pr.n_joints)
     s = ChainSolver(pr, T, B, dtype=dt, linearization=lin, device=device)
     s.set_dynamics(dynamics)
+    if simple_cost:  # cost_functions.jl's pair: the tool point's squared distance to a reachable target
+        s.set_simple_costs(pr.n_joints - 1, SIMPLE_COST["point"], SIMPLE_COST["final_target"],
+                           SIMPLE_COST["weight"], euclidean=True)
     u = torch.zeros((B, T, pr.nu), dtype=dt, device=dev)
     x = s.rollout(torch.from_numpy(x0).to(dev, dt), u)
     xn, un = torch.empty_like(x), torch.empty_like(u)
@@ -157,6 +162,7 @@ def measure(lin="fd", B=2048, T=100, nu=1, dtype="f32", steps=100, warmup=100, d
                                    f"gravity {[float(v) for v in pr.chain.gravity]})" if six else
                                    "BASELINE config 5 (RBD_2_link_example, fixed base)"),
                       "batch": B, "T": T, "linearization": lin, "dynamics": s.dynamics_mode,
+                      "cost_mode": s.cost_mode,
                       "closed_form_check": s.closed_form_error},
            "traj_iters_per_s": B * 1000.0 / ms,
            "mean_line_search_trials": float(trials.double().mean().item()), "all_ok": ok,
@@ -213,6 +219,9 @@ def main():
     ap.add_argument("--gravity", action="store_true", help="6dof_arm: gravity (0, 0, -9.81) on")
     ap.add_argument("--dynamics", default="auto", choices=["auto", "rnea", "closed_form"],
                     help="the chain handle's dynamics evaluator (ilqr_chain_set_dynamics)")
+    ap.add_argument("--simple-cost", action="store_true",
+                    help="6dof_arm: cost_functions.jl's task-space costs (ilqr_chain_set_task_costs) in place "
+                         "of the joint-space ones; no CPU baseline (the C restatement has the joint costs)")
     args = ap.parse_args()
     base = None
     problem = None
@@ -222,10 +231,13 @@ def main():
         problem = rbd_6dof_problem(gravity=args.gravity)
     elif args.gravity:
         ap.error("--gravity goes with --robot 6dof_arm")
+    if args.simple_cost and args.robot != "6dof_arm":
+        ap.error("--simple-cost goes with --robot 6dof_arm")
     for lin in args.lin.split(","):
         res = measure(lin, args.batch, args.T, args.nu, args.dtype, args.steps, args.warmup,
-                      dynamics=args.dynamics, cpu_budget=None if args.no_cpu else args.cpu_budget, base=base,
-                      problem=problem)
+                      dynamics=args.dynamics,
+                      cpu_budget=None if args.no_cpu or args.simple_cost else args.cpu_budget, base=base,
+                      problem=problem, simple_cost=args.simple_cost)
         base = res["cpu_baseline"]
         print(json.dumps(res), flush=True)
 
