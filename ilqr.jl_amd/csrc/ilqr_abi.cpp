@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/ilqr.h"
+#include "ilqr_fit.h"
 #include "ilqr_internal.h"
 
 constexpr int BW4_MIN_BATCH = 2048;  // default backward kernel switch (see bw_wave)
@@ -27,22 +28,8 @@ struct ilqr_handle {
   double* ubuf[2] = {nullptr, nullptr};
   double* K = nullptr;
   double* d = nullptr;
-  double* prev_cost = nullptr;
-  double* du2 = nullptr;
-  int32_t* trials = nullptr;
-  int32_t* status = nullptr;
-  int32_t* res_parity = nullptr;
-  int32_t* iters = nullptr;
+  ilqr::FitState fit;              // the fit driver's per-trajectory state, words and events (ilqr_fit.h)
   int32_t* host_status = nullptr;  // pinned host copy of a status array (fold_status)
-  // fit's convergence poll: running-trajectory counts of the last two iterations,
-  // written by the device into host-mapped memory, each behind an event
-  // [2] = fit's call-status flags (gather_kernel: bit 0 NaN, bit 1 exhausted line search)
-  int32_t* host_running = nullptr;
-  int32_t* dev_running = nullptr;  // device alias of host_running
-  int32_t* dev_flags = nullptr;    // gather_kernel's device call-status word
-  hipEvent_t ev_poll[2] = {nullptr, nullptr};
-  ilqr::HostWait host_wait;        // the end-of-fit wait (wait_host_seq)
-  ilqr::HostWait poll_wait;        // the per-iteration convergence polls (wait_event)
   // LQ problems of another shape (nx ≤ 12, nu ≤ 4) run zero-padded on an inner
   // (12, 4) handle (created on the first such call): zero rows/columns of A, B, Q, R,
   // Qf, x, u decouple exactly, so the real entries are the (12, 4) kernels' bits.
@@ -89,7 +76,6 @@ struct ilqr_handle {
   uint64_t* coop_list = nullptr;
   int32_t* coop_ctl = nullptr;
   uint32_t coop_gen = 0;  // fused launches so far (the list's generation tag)
-  uint32_t fit_seq = 0;   // fits so far (tags the host call-status word, wait_fit)
   double* coop_sx = nullptr;  // the search's scratch rollouts (LSCoop::sx / su)
   double* coop_su = nullptr;
   ilqr::LSCoop* coop_dev = nullptr;  // the struct of the above, in device memory
@@ -331,13 +317,6 @@ ilqr_status unpad_u(ilqr_handle* h, const double* pu, double* u) {
   return unpad3(h, pu, u, (size_t)h->batch, h->T, h->nu, h->T, PAD_NU);
 }
 
-// The end of a fit: the stream's last kernel stores this fit's number into a wait word
-// (ilqr::wait_host_seq below).
-// `units`: the fit iterations enqueued since the host last waited on this fit.
-hipError_t wait_fit(ilqr_handle* h, uint32_t seq, int units, hipStream_t s) {
-  return ilqr::wait_host_seq(h->host_running + 2, seq, units, s, &h->host_wait);
-}
-
 }  // namespace
 
 // The stream's last kernel of a fit (gather_flags_kernel) stores the fit's number into
@@ -430,19 +409,8 @@ ilqr_status ilqr_create(ilqr_handle** out, int device, int nx, int nu, int T, in
   }
   if (e == hipSuccess) e = hipMalloc(&h->K, sizeof(double) * B * T * nu * nx);
   if (e == hipSuccess) e = hipMalloc(&h->d, sizeof(double) * B * T * nu);
-  if (e == hipSuccess) e = hipMalloc(&h->prev_cost, sizeof(double) * B);
-  if (e == hipSuccess) e = hipMalloc(&h->du2, sizeof(double) * B);
-  if (e == hipSuccess) e = hipMalloc(&h->trials, sizeof(int32_t) * B);
-  if (e == hipSuccess) e = hipMalloc(&h->status, sizeof(int32_t) * B);
-  if (e == hipSuccess) e = hipMalloc(&h->res_parity, sizeof(int32_t) * B);
-  if (e == hipSuccess) e = hipMalloc(&h->iters, sizeof(int32_t) * B);
+  if (e == hipSuccess) e = ilqr::fit_state_create(&h->fit, B, sizeof(double));
   if (e == hipSuccess) e = hipHostMalloc(&h->host_status, sizeof(int32_t) * B, hipHostMallocDefault);
-  if (e == hipSuccess)
-    e = hipHostMalloc(&h->host_running, sizeof(int32_t) * 4, hipHostMallocMapped | hipHostMallocCoherent);
-  if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&h->dev_running, h->host_running, 0);
-  if (e == hipSuccess) e = hipMalloc(&h->dev_flags, sizeof(int32_t) * 2);
-  if (e == hipSuccess) e = hipMemset(h->dev_flags, 0, sizeof(int32_t) * 2);
-  for (int c = 0; c < 2 && e == hipSuccess; ++c) e = hipEventCreateWithFlags(&h->ev_poll[c], hipEventDisableTiming);
   if (e == hipSuccess && nx == 12 && nu == 4) {
     e = hipMalloc(&h->coop_rec, sizeof(ilqr::LSCoopRec) * B);
     if (e == hipSuccess) e = hipMalloc(&h->coop_cost, sizeof(double) * B * ilqr::COOP_MAX_TRIALS);
@@ -519,15 +487,8 @@ ilqr_status ilqr_destroy(ilqr_handle* h) {
   }
   (void)hipFree(h->K);
   (void)hipFree(h->d);
-  (void)hipFree(h->prev_cost);
-  (void)hipFree(h->du2);
-  (void)hipFree(h->trials);
-  (void)hipFree(h->status);
-  (void)hipFree(h->res_parity);
-  (void)hipFree(h->iters);
+  ilqr::fit_state_destroy(&h->fit);
   if (h->host_status) (void)hipHostFree(h->host_status);
-  if (h->host_running) (void)hipHostFree(h->host_running);
-  (void)hipFree(h->dev_flags);
   (void)hipFree(h->coop_rec);
   (void)hipFree(h->coop_cost);
   (void)hipFree(h->coop_du2);
@@ -537,8 +498,6 @@ ilqr_status ilqr_destroy(ilqr_handle* h) {
   (void)hipFree(h->coop_ctl);
   (void)hipFree(h->coop_dev);
   (void)hipFree(h->fac);
-  for (int c = 0; c < 2; ++c)
-    if (h->ev_poll[c]) (void)hipEventDestroy(h->ev_poll[c]);
   if (h->pad) {
     (void)ilqr_destroy(h->pad);
     for (double* q : {h->pA, h->pB, h->pQ, h->pR, h->pQf, h->px, h->pu, h->pxt, h->pxn, h->pun, h->pd, h->pK})
@@ -772,52 +731,38 @@ ilqr_status ilqr_fit_ex(ilqr_handle* h, const ilqr_problem* p, const ilqr_option
     return fst;
   }
   hipStream_t s = h->stream;
-  // prev_cost = Inf (forward_pass.jl:159), status OK, result "the input", iters 0: by
-  // the first iteration's kernel itself on the fused LQ path, else by a kernel here
+  ilqr::FitState& f = h->fit;
   // the pipelined schedule interleaves two iterations per launch: a fit that records
   // its history runs the sequential schedule instead (the same bits)
   const bool pipe = !two_link(p) && h->pipelined && !hist;
+  // the per-trajectory state is set by the first iteration's kernel itself on the fused
+  // LQ path, else by fit_begin's launch
   const bool init_in_iter = fused_path(h, p) && !pipe && o->max_iter > 0;
-  if (!init_in_iter)
-    HIP_TRY(ilqr::launch_fit_init(h->batch, h->prev_cost, h->status, h->res_parity, h->iters, s));
-  volatile int32_t* flags = h->host_running + 2;
-  *flags = 0;
   const ilqr::LSParams ls = ilqr::ls_params(o);
-  // Iteration `it` reads x̄ⁱ (the caller's x_init/u_init for it = 1, no copy; else
-  // the handle's buffer (it−1)&1) and writes buffer it&1 (x̄ⁱ, ūⁱ = x̄ⁱ⁺¹, ūⁱ⁺¹,
-  // :174-175). `parity` records where a trajectory's result lies when it stops:
-  // ilqr::PARITY_INPUT for the caller's buffers.
-  // The last iteration writes the caller's x_out / u_out directly (the gather then
-  // copies only trajectories that stopped earlier) unless they overlap an input.
-  const size_t xbytes = sizeof(double) * (size_t)h->batch * (h->T + 1) * h->nx;
-  const size_t ubytes = sizeof(double) * (size_t)h->batch * h->T * h->nu;
-  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
-    const char *pa = (const char*)a, *pb = (const char*)b;
-    return b && pa < pb + nb && pb < pa + na;
-  };
-  const bool direct = o->max_iter > 0 && !overlap(x_out, xbytes, x_init, xbytes) &&
-                      !overlap(x_out, xbytes, x_traj, xbytes) && !overlap(u_out, ubytes, u_init, ubytes) &&
-                      !overlap(x_out, xbytes, u_init, ubytes) && !overlap(u_out, ubytes, x_init, xbytes) &&
-                      !overlap(u_out, ubytes, x_traj, xbytes);
+  ilqr::FitCall c;
+  c.B = h->batch, c.T = h->T, c.nx = h->nx, c.nu = h->nu;
+  c.max_iter = o->max_iter;
+  c.x_init = x_init, c.u_init = u_init, c.x_out = x_out, c.u_out = u_out;
+  for (int i = 0; i < 2; ++i) c.xbuf[i] = h->xbuf[i], c.ubuf[i] = h->ubuf[i];
+  HIP_TRY(ilqr::fit_begin(f, c, x_traj, o->tol, /*init=*/!init_in_iter, s));
   auto iter_args = [&](int it) {
-    const int par = (it - 1) & 1;
-    const bool last = direct && it == o->max_iter;
+    const ilqr::FitBuffers b = ilqr::fit_buffers(c, it);
     ilqr::IterArgs a{};
-    a.x = it == 1 ? x_init : h->xbuf[par];
-    a.u = it == 1 ? u_init : h->ubuf[par];
+    a.x = (const double*)b.x;
+    a.u = (const double*)b.u;
     a.xtraj = x_traj;
-    a.xnew = last ? x_out : h->xbuf[par ^ 1];
-    a.unew = last ? u_out : h->ubuf[par ^ 1];
+    a.xnew = (double*)b.xnew;
+    a.unew = (double*)b.unew;
     a.K = h->K;
     a.d = h->d;
-    a.prev_cost = h->prev_cost;  // in place: prev_cost = new_cost (:168)
-    a.new_cost = h->prev_cost;
-    a.du2 = h->du2;
-    a.trials = h->trials;
-    a.status = h->status;
-    a.res_parity = h->res_parity;
-    a.iters = h->iters;
-    a.parity = it == 1 ? ilqr::PARITY_INPUT : par;
+    a.prev_cost = (const double*)f.prev_cost;  // in place: prev_cost = new_cost (:168)
+    a.new_cost = (double*)f.prev_cost;
+    a.du2 = (double*)f.du2;
+    a.trials = f.trials;
+    a.status = f.status;
+    a.res_parity = f.res_parity;
+    a.iters = f.iters;
+    a.parity = b.parity;
     a.iter = it;
     a.init = init_in_iter && it == 1;
     // gain reuse, decided per call: iteration 1 runs the full recursion and stores the
@@ -837,19 +782,12 @@ ilqr_status ilqr_fit_ex(ilqr_handle* h, const ilqr_problem* p, const ilqr_option
       HIP_TRY(ilqr::launch_lq_iter_pipe(h->nx, h->nu, lq_params(p), h->batch, h->T, iter_args(it),
                                         iter_args(it - 1), ls, flags, s));
     }
+    c.enqueued = o->max_iter;
   }
-  // With a convergence test (tol ≥ 0) the loop stops enqueueing once every trajectory
-  // has stopped, like the reference's `break` (:171): after iteration it a one-block
-  // kernel writes the running count to host-mapped memory behind an event, and the host
-  // reads iteration it−1's count while the GPU runs iteration it (no idle gap; at most
-  // one iteration of already-stopped waves is enqueued past the last useful one).
-  const bool poll = o->tol >= 0.0 && o->max_iter > 2;
-  int enqueued = pipe ? o->max_iter : 0, waited = 0;  // iterations (the end-of-fit wait's units)
   for (int it = 1; !pipe && it <= o->max_iter; ++it) {  // forward_pass.jl:161
     // iterations chain per chunk: chunk 0's next backward overlaps chunk 1's forward
     const ilqr_status st = enqueue_iteration(h, p, iter_args(it), ls, /*chain=*/true, hist);
     if (st != ILQR_OK) return st;
-    enqueued = it;
     // the history record and the count run behind every chunk's forward without
     // joining the main stream (a join would keep chunk 0's next backward from
     // overlapping chunk 1's forward): the forwards of all chunks are in order on the
@@ -857,34 +795,16 @@ ilqr_status ilqr_fit_ex(ilqr_handle* h, const ilqr_problem* p, const ilqr_option
     const hipStream_t ps = (two_link(p) || h->nchunks == 1) ? s : h->side;
     // (chunked: enqueue_iteration recorded each chunk right behind its forward)
     if (hist && ps == s)
-      HIP_TRY(ilqr::launch_record_history(h->batch, it, h->status, h->iters, h->trials, h->prev_cost, h->du2,
-                                          false, ls.alpha0, ls.shrink, hist->cost, hist->trials, hist->alpha,
+      HIP_TRY(ilqr::launch_record_history(h->batch, it, f.status, f.iters, f.trials, f.prev_cost, f.du2, false,
+                                          ls.alpha0, ls.shrink, hist->cost, hist->trials, hist->alpha,
                                           hist->du2, ps));
-    if (!poll || it == o->max_iter) continue;
-    HIP_TRY(ilqr::launch_count_running(h->batch, h->status, h->dev_running + (it & 1), ps));
-    HIP_TRY(hipEventRecord(h->ev_poll[it & 1], ps));
-    if (it >= 2) {
-      HIP_TRY(ilqr::wait_event(h->ev_poll[(it - 1) & 1], &h->poll_wait));
-      waited = it - 1;
-      if (__atomic_load_n(h->host_running + ((it - 1) & 1), __ATOMIC_ACQUIRE) == 0) break;
-    }
+    bool stopped;
+    HIP_TRY(ilqr::fit_poll(f, c, it, ps, &stopped));
+    if (stopped) break;
   }
-  {
-    const ilqr_status st = join(h, p);
-    if (st != ILQR_OK) return st;
-  }
-  // still-running trajectories (max_iter reached) return the last accepted iterate,
-  // the one the last iteration wrote (the input when max_iter = 0)
-  const int last = o->max_iter == 0 ? ilqr::PARITY_INPUT : (direct ? ilqr::PARITY_OUT : (o->max_iter & 1));
-  uint32_t seq = (++h->fit_seq) & 0x3fffffffu;
-  if (seq == 0) seq = h->fit_seq = 1;  // 0 is the word's cleared value
-  HIP_TRY(ilqr::launch_gather_result(h->batch, h->T, h->nx, h->nu, x_init, u_init, h->xbuf[0],
-                                     h->ubuf[0], h->xbuf[1], h->ubuf[1], h->res_parity, h->status,
-                                     last, h->prev_cost, h->iters, x_out, u_out, cost, iters,
-                                     status, h->dev_flags, h->dev_running + 2, s, seq));
-  HIP_TRY(wait_fit(h, seq, enqueued - waited, s));
-  const int32_t f = __atomic_load_n(h->host_running + 2, __ATOMIC_ACQUIRE);
-  return (f & 1) ? ILQR_ERR_NAN : ((f & 2) ? ILQR_ERR_LS_EXHAUSTED : ILQR_OK);
+  ILQR_TRY(join(h, p));
+  HIP_TRY(ilqr::fit_end(f, c, cost, iters, status, s, &st));
+  return st;
 }
 
 ilqr_status ilqr_malloc(ilqr_handle* h, size_t bytes, void** ptr) {

@@ -43,6 +43,7 @@
 #include <type_traits>
 
 #include "../../include/ilqr.h"
+#include "ilqr_fit.h"
 #include "ilqr_internal.h"
 #include "ilqr_device.h"
 #include "ilqr_math.h"
@@ -1287,176 +1288,6 @@ __global__ __launch_bounds__(256) void chain_unpack_kernel(int B, int T, const V
 }
 
 // ---------------------------------------------------------------------------
-// Riccati recursion (src/backward_pass.jl:324-357), one lane per trajectory
-// ---------------------------------------------------------------------------
-template <class V, int NJ, int NU>
-__device__ bool chain_backward_lane(const ChainK<V, NJ>& P, int b, int T, const V* __restrict__ x,
-                                    const V* __restrict__ J, V* __restrict__ dg,
-                                    V* __restrict__ Kg, V mu) {
-  constexpr int NX = 2 * NJ, ND = NX + NU, NR = Rec<NJ, NU>::N, NJAC = Rec<NJ, NU>::NJAC;
-  const V* xN = x + ((size_t)b * (T + 1) + T) * NX;
-  // final_cost_quadratization (:134-153): ∇ℓ_f = −2 qfw (θ* − θ), ∇²ℓ_f = diag(2 qfw, 0)
-  V S[NX][NX], s[NX];
-#pragma unroll
-  for (int i = 0; i < NX; ++i) {
-#pragma unroll
-    for (int j = 0; j < NX; ++j) S[i][j] = V(0);
-    s[i] = V(0);
-  }
-#pragma unroll
-  for (int i = 0; i < NJ; ++i) {
-    S[i][i] = V(2) * P.qfw[i];
-    s[i] = V(-2) * P.qfw[i] * (P.tgt[i] - xN[i]);
-  }
-  bool bad = false;
-  const V* Jb = J + (size_t)b * T * NR;
-  V rec[2][NR];
-  auto load = [&](int t, V (&r)[NR]) {
-    const V* Jt = Jb + (size_t)(t > 0 ? t : 0) * NR;
-#pragma unroll
-    for (int k = 0; k < NR; ++k) r[k] = Jt[k];
-  };
-  auto step = [&](int t, const V (&F)[NR]) {
-    // Y = S F, sF = sᵀF  (optimal_controller_param :181-183)
-    V Y[NX][ND], sF[ND];
-#pragma unroll
-    for (int i = 0; i < NX; ++i)
-#pragma unroll
-      for (int k = 0; k < ND; ++k) {
-        V acc = V(0);
-#pragma unroll
-        for (int j = 0; j < NX; ++j) acc = fma(S[i][j], F[j * ND + k], acc);
-        Y[i][k] = acc;
-      }
-#pragma unroll
-    for (int k = 0; k < ND; ++k) {
-      V acc = V(0);
-#pragma unroll
-      for (int j = 0; j < NX; ++j) acc = fma(s[j], F[j * ND + k], acc);
-      sF[k] = acc;
-    }
-    auto Z = [&](int a, int c) {
-      V acc = V(0);
-#pragma unroll
-      for (int j = 0; j < NX; ++j) acc = fma(F[j * ND + a], Y[j][c], acc);
-      return acc;
-    };
-    // immediate_cost_quadratization (:81-109): lx = −2qw(θ*−θ), lu = 2 rw u,
-    // lxx = diag(2qw, 0), luu = diag(2rw), lux = 0
-    V G[NU][NX], H[NU][NU], g[NU];
-#pragma unroll
-    for (int a = 0; a < NU; ++a) {
-#pragma unroll
-      for (int c = 0; c < NX; ++c) G[a][c] = Z(NX + a, c);
-#pragma unroll
-      for (int c = 0; c < NU; ++c) H[a][c] = Z(NX + a, NX + c) + (a == c ? V(2) * P.rw[a] : V(0));
-      g[a] = V(2) * P.rw[a] * F[NJAC + NX + a] + sF[NX + a];
-    }
-    // feedback_parameters (:207-218): H + μI = L D Lᵀ (unit lower L); δu = −H⁻¹g, K = −H⁻¹G
-    V L[NU][NU], D[NU], iD[NU];
-#pragma unroll
-    for (int i = 0; i < NU; ++i) {
-#pragma unroll
-      for (int j = 0; j < i; ++j) {
-        V acc = H[i][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) acc = acc - L[i][k] * L[j][k] * D[k];
-        L[i][j] = acc * iD[j];
-      }
-      V acc = H[i][i] + mu;
-#pragma unroll
-      for (int k = 0; k < i; ++k) acc = acc - L[i][k] * L[i][k] * D[k];
-      D[i] = acc;
-      iD[i] = V(1) / acc;
-    }
-    auto solve = [&](const V (&r)[NU], V (&z)[NU]) {  // z = −(H + μI)⁻¹ r
-      V y[NU], w[NU];
-#pragma unroll
-      for (int i = 0; i < NU; ++i) {
-        V acc = r[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) acc = acc - L[i][k] * y[k];
-        y[i] = acc;
-      }
-#pragma unroll
-      for (int i = NU - 1; i >= 0; --i) {
-        V acc = y[i] * iD[i];
-#pragma unroll
-        for (int k = i + 1; k < NU; ++k) acc = acc - L[k][i] * w[k];
-        w[i] = acc;
-      }
-#pragma unroll
-      for (int i = 0; i < NU; ++i) z[i] = -w[i];
-    };
-    V K[NU][NX], d[NU];
-#pragma unroll
-    for (int c = 0; c < NX; ++c) {
-      V r[NU], z[NU];
-#pragma unroll
-      for (int a = 0; a < NU; ++a) r[a] = G[a][c];
-      solve(r, z);
-#pragma unroll
-      for (int a = 0; a < NU; ++a) K[a][c] = z[a];
-    }
-    solve(g, d);
-    V* Kt = Kg + ((size_t)b * T + t) * NU * NX;
-    V* dt = dg + ((size_t)b * T + t) * NU;
-#pragma unroll
-    for (int a = 0; a < NU; ++a) {
-      dt[a] = d[a];
-      bad |= d[a] != d[a];
-#pragma unroll
-      for (int c = 0; c < NX; ++c) {
-        Kt[a * NX + c] = K[a][c];
-        bad |= K[a][c] != K[a][c];
-      }
-    }
-    // step_back (:262-273), exact rewrite with W = (H+2μI)[K|d] = −[G|g] + μ[K|d]
-    V WK[NU][NX], Wd[NU];
-#pragma unroll
-    for (int a = 0; a < NU; ++a) {
-#pragma unroll
-      for (int c = 0; c < NX; ++c) WK[a][c] = fma(mu, K[a][c], -G[a][c]);
-      Wd[a] = fma(mu, d[a], -g[a]);
-    }
-    V Sn[NX][NX], sn[NX];
-#pragma unroll
-    for (int i = 0; i < NX; ++i) {
-#pragma unroll
-      for (int j = i; j < NX; ++j) {
-        V acc = Z(i, j);
-        if (i == j && i < NJ) acc += V(2) * P.qw[i];
-#pragma unroll
-        for (int a = 0; a < NU; ++a) acc = fma(-K[a][i], WK[a][j], acc);
-        Sn[i][j] = acc;
-        Sn[j][i] = acc;
-      }
-      V acc = sF[i];
-      if (i < NJ) acc += V(-2) * P.qw[i] * (P.tgt[i] - F[NJAC + i]);
-#pragma unroll
-      for (int a = 0; a < NU; ++a) acc = fma(-K[a][i], Wd[a], acc);
-      sn[i] = acc;
-    }
-#pragma unroll
-    for (int i = 0; i < NX; ++i) {
-      s[i] = sn[i];
-#pragma unroll
-      for (int j = 0; j < NX; ++j) S[i][j] = Sn[i][j];
-    }
-  };
-  load(T - 1, rec[0]);
-  int t = T - 1;
-  for (; t >= 1; t -= 2) {  // one step of prefetch
-    load(t - 1, rec[1]);
-    step(t, rec[0]);
-    load(t - 2, rec[0]);
-    step(t - 1, rec[1]);
-  }
-  if (t == 0) step(0, rec[0]);
-  return bad;
-}
-
-// ---------------------------------------------------------------------------
 // Forward rollout + line search (src/forward_pass.jl:55-93), one lane per trajectory
 // ---------------------------------------------------------------------------
 template <class V>
@@ -1768,18 +1599,6 @@ __device__ __forceinline__ void chain_consts_to_lds(PK& Ps, const PK& P) {
   __syncthreads();
 }
 
-template <class V, int NJ, int NU>
-__global__ __launch_bounds__(CH_WG) void chain_backward_kernel(ChainK<V, NJ> P, int B, int T,
-                                                               const V* __restrict__ x,
-                                                               const V* __restrict__ J,
-                                                               V* __restrict__ d, V* __restrict__ K,
-                                                               int32_t* __restrict__ status, V mu) {
-  const int b = blockIdx.x * CH_WG + threadIdx.x;
-  if (b >= B) return;
-  const bool nan = chain_backward_lane<V, NJ, NU>(P, b, T, x, J, d, K, mu);
-  if (status) status[b] = nan ? ILQR_TRAJ_NAN : ILQR_TRAJ_OK;
-}
-
 // lanes per trajectory of the forward kernels: a 16-lane group (one DPP row) running
 // the component-parallel Newton-Euler (chain_xdot_cv)
 constexpr int CH_FW_LANES = 16;
@@ -1825,17 +1644,6 @@ __global__ __launch_bounds__(CH_WG) void chain_forward_kernel(
   if (trials) trials[b] = r.trials;
   if (status) status[b] = r.accepted ? ILQR_TRAJ_OK
                                      : (r.cost != r.cost ? ILQR_TRAJ_NAN : ILQR_TRAJ_LS_EXHAUSTED);
-}
-
-template <class V, int NJ, int NU>
-__global__ __launch_bounds__(CH_WG) void chain_iter_backward_kernel(ChainK<V, NJ> P, int B, int T,
-                                                                    ChainIter<V> a, const V* J, V mu) {
-  const int b = blockIdx.x * CH_WG + threadIdx.x;
-  if (b >= B || a.status[b] != ILQR_TRAJ_OK) return;
-  if (chain_backward_lane<V, NJ, NU>(P, b, T, a.x, J, a.d, a.K, mu)) {
-    a.status[b] = ILQR_TRAJ_NAN;  // reference: AssertionError at backward_pass.jl:353
-    if (a.res_parity) a.res_parity[b] = a.parity;
-  }
 }
 
 // fit iteration, backward part, 2-joint chains: slots whose status is not OK are
@@ -1968,58 +1776,6 @@ __global__ __launch_bounds__(64 * W) void chain_iter_forward_trig_kernel(ChainTr
   fwd_iter_finish(a, b, r.cost, r.accepted, r.trials, r.du2, ls.tol);
 }
 
-// The end of a chain fit (the LQ driver's gather_kernel for V = float / double): x_out[b]
-// = the buffer res_parity[b] names — x0 / x1 the handle's, PARITY_INPUT the caller's
-// x_init, PARITY_OUT nothing to copy (the last iteration wrote x_out) — with
-// final_parity for still-running trajectories, whose status becomes MAX_ITER; cost /
-// iterations / status copied out (each may be null); the call-status bits (1 NaN,
-// 2 exhausted search) OR-ed into dflags[0] by the trajectories that set one. One block
-// per trajectory: status is read by every thread before thread 0 rewrites it.
-template <class V>
-__global__ __launch_bounds__(256) void chain_gather_kernel(int B, int nxe, int nue, const V* xin, const V* uin,
-                                                           const V* x0, const V* u0, const V* x1, const V* u1,
-                                                           const int32_t* res_parity, int32_t* status,
-                                                           int final_parity, const V* fit_cost,
-                                                           const int32_t* fit_iters, V* x_out, V* u_out,
-                                                           V* cost_out, int32_t* iters_out, int32_t* status_out,
-                                                           int32_t* dflags) {
-  const int b = blockIdx.y;
-  if (b >= B) return;
-  const int32_t st0 = status[b];
-  const bool running = st0 == ILQR_TRAJ_OK;
-  const int par = running ? final_parity : res_parity[b];
-  if (par != PARITY_OUT) {
-    const V* xs = (par == PARITY_INPUT ? xin : (par ? x1 : x0)) + (size_t)b * nxe;
-    const V* us = (par == PARITY_INPUT ? uin : (par ? u1 : u0)) + (size_t)b * nue;
-    for (int i = threadIdx.x; i < nxe + nue; i += 256) {
-      if (i < nxe) x_out[(size_t)b * nxe + i] = xs[i];
-      else u_out[(size_t)b * nue + (i - nxe)] = us[i - nxe];
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int32_t st = running ? ILQR_TRAJ_MAX_ITER : st0;
-    status[b] = st;
-    if (status_out) status_out[b] = st;
-    if (cost_out) cost_out[b] = fit_cost[b];
-    if (iters_out) iters_out[b] = fit_iters[b];
-    const int f = (st == ILQR_TRAJ_NAN ? 1 : 0) | (st == ILQR_TRAJ_LS_EXHAUSTED ? 2 : 0);
-    if (f) __hip_atomic_fetch_or(dflags, f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// fit's per-trajectory state (forward_pass.jl:159): prev_cost = +Inf, status OK, result
-// "the input" (iteration 1 reads x_init / u_init in place), iterations 0 — one launch
-template <class V>
-__global__ void chain_fit_init_kernel(int B, V* prev_cost, int32_t* status, int32_t* res_parity, int32_t* iters) {
-  const int b = blockIdx.x * 256 + threadIdx.x;
-  if (b >= B) return;
-  prev_cost[b] = V(INFINITY);
-  status[b] = ILQR_TRAJ_OK;
-  res_parity[b] = PARITY_INPUT;
-  iters[b] = 0;
-}
-
 // ---------------------------------------------------------------------------
 // Six-joint chains (the 6-DoF arm, nx = 12, nu = 6, fp64). The Riccati recursion is the
 // wide tiles kernel (launch_tiles_backward, ilqr_tiles.hip), so the linearisation and the
@@ -2101,7 +1857,7 @@ struct ChainCostK {
   double tgt[NJ], qw[NJ], rw[NJ], qfw[NJ];
 };
 
-// The cost tiles that change with (x, u), exactly as chain_backward_lane forms them
+// The cost tiles that change with (x, u), the terms chain_backward4_wave forms for two joints
 // (immediate_cost_quadratization :81-109, final_cost_quadratization :134-153):
 // lx = −2qw(θ* − θ) on the joint rows, lu = 2rw·u, lfx = −2qfw(θ* − θ_N).
 // One lane per element: (b, t ≤ T, e < NX + NU), t = T the terminal row.
@@ -2500,12 +2256,19 @@ __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P
 
 constexpr int CH6_WG = 64;  // two trajectories per workgroup (one wave)
 
-template <int NJ, int NU>
+// The two forward kernels. TaskK is empty (the joint-space cost) or ChainTaskK (a task mode:
+// the TASK instantiation of the group, the task cost's constants one more kernel argument).
+// As a pack it adds nothing to the joint-cost kernels' argument list, so both modes keep the
+// kernel arguments, and with them the code, that each had as a kernel written out. A pack in
+// the middle of the list is never deduced: every launch spells out <NJ, NU> or
+// <NJ, NU, ChainTaskK>.
+template <int NJ, int NU, class... TaskK>
 __global__ __launch_bounds__(CH6_WG) void chain_forward32_kernel(
-    ChainK<double, NJ> P, int B, int T, const double* __restrict__ x, const double* __restrict__ u,
+    ChainK<double, NJ> P, TaskK... C, int B, int T, const double* __restrict__ x, const double* __restrict__ u,
     const double* __restrict__ xtraj, const double* __restrict__ d, const double* __restrict__ K,
     const double* __restrict__ prev_cost, double* __restrict__ xnew, double* __restrict__ unew,
     double* __restrict__ new_cost, int32_t* __restrict__ trials, int32_t* __restrict__ status, LSParams ls) {
+  static_assert((std::is_same_v<TaskK, ChainTaskK> && ...) && sizeof...(TaskK) <= 1, "TaskK: none or ChainTaskK");
   __shared__ ChainK<double, NJ> Ps;
   __shared__ double stage[(CH6_WG / CH6_LANES) * CH6_STAGE];
   chain_consts_to_lds<CH6_WG>(Ps, P);
@@ -2513,8 +2276,8 @@ __global__ __launch_bounds__(CH6_WG) void chain_forward32_kernel(
   if (b >= B) return;  // the whole lane group
   const int l32 = threadIdx.x & (CH6_LANES - 1);
   const double pc = prev_cost ? prev_cost[b] : (double)INFINITY;
-  const ChainFwdOut<double> r = chain_forward_group32<NJ, NU>(
-      Ps, stage + (threadIdx.x / CH6_LANES) * CH6_STAGE, b, T, x, u, xtraj, d, K, pc, xnew, unew, nullptr, ls);
+  const ChainFwdOut<double> r = chain_forward_group32<NJ, NU, sizeof...(TaskK) == 1>(
+      Ps, stage + (threadIdx.x / CH6_LANES) * CH6_STAGE, b, T, x, u, xtraj, d, K, pc, xnew, unew, nullptr, ls, C...);
   // every lane of the group: the 32 lanes stride the copy of an exhausted search's inputs
   fwd_finish<2 * NJ, NU>(b, T, r.cost, r.trials, r.accepted, x, u, xnew, unew, l32, CH6_LANES, new_cost, trials,
                          status);
@@ -2522,12 +2285,13 @@ __global__ __launch_bounds__(CH6_WG) void chain_forward32_kernel(
 
 // fit iteration, forward part. bstatus is the tiles kernel's per-trajectory result of this
 // iteration's backward pass (it runs every trajectory): a NaN gain of a running
-// trajectory ends it here, as chain_iter_backward_kernel does
-template <int NJ, int NU>
-__global__ __launch_bounds__(CH6_WG) void chain_iter_forward32_kernel(ChainK<double, NJ> P, int B, int T,
+// trajectory ends it here, as chain_iter_backward4_kernel does
+template <int NJ, int NU, class... TaskK>
+__global__ __launch_bounds__(CH6_WG) void chain_iter_forward32_kernel(ChainK<double, NJ> P, TaskK... C, int B, int T,
                                                                      ChainIter<double> a,
                                                                      const int32_t* __restrict__ bstatus,
                                                                      LSParams ls) {
+  static_assert((std::is_same_v<TaskK, ChainTaskK> && ...) && sizeof...(TaskK) <= 1, "TaskK: none or ChainTaskK");
   __shared__ ChainK<double, NJ> Ps;
   __shared__ double stage[(CH6_WG / CH6_LANES) * CH6_STAGE];
   chain_consts_to_lds<CH6_WG>(Ps, P);
@@ -2543,58 +2307,9 @@ __global__ __launch_bounds__(CH6_WG) void chain_iter_forward32_kernel(ChainK<dou
   }
   double du2 = 0.0;
   const double pc = a.prev_cost ? a.prev_cost[b] : (double)INFINITY;
-  const ChainFwdOut<double> r =
-      chain_forward_group32<NJ, NU>(Ps, stage + (threadIdx.x / CH6_LANES) * CH6_STAGE, b, T, a.x, a.u, a.xtraj,
-                                    a.d, a.K, pc, a.xnew, a.unew, &du2, ls);
-  if (l32 != 0) return;
-  fwd_iter_finish(a, b, r.cost, r.accepted, r.trials, du2, ls.tol);
-}
-
-// The two forward kernels in a task mode: the same bodies on the TASK instantiation of the
-// group, the task cost's constants one more kernel argument. Kernels of their own, so the
-// joint-cost kernels above are the code they were.
-template <int NJ, int NU>
-__global__ __launch_bounds__(CH6_WG) void chain_forward32_task_kernel(
-    ChainK<double, NJ> P, ChainTaskK C, int B, int T, const double* __restrict__ x, const double* __restrict__ u,
-    const double* __restrict__ xtraj, const double* __restrict__ d, const double* __restrict__ K,
-    const double* __restrict__ prev_cost, double* __restrict__ xnew, double* __restrict__ unew,
-    double* __restrict__ new_cost, int32_t* __restrict__ trials, int32_t* __restrict__ status, LSParams ls) {
-  __shared__ ChainK<double, NJ> Ps;
-  __shared__ double stage[(CH6_WG / CH6_LANES) * CH6_STAGE];
-  chain_consts_to_lds<CH6_WG>(Ps, P);
-  const int b = (blockIdx.x * CH6_WG + threadIdx.x) / CH6_LANES;
-  if (b >= B) return;  // the whole lane group
-  const int l32 = threadIdx.x & (CH6_LANES - 1);
-  const double pc = prev_cost ? prev_cost[b] : (double)INFINITY;
-  const ChainFwdOut<double> r = chain_forward_group32<NJ, NU, true>(
-      Ps, stage + (threadIdx.x / CH6_LANES) * CH6_STAGE, b, T, x, u, xtraj, d, K, pc, xnew, unew, nullptr, ls, C);
-  fwd_finish<2 * NJ, NU>(b, T, r.cost, r.trials, r.accepted, x, u, xnew, unew, l32, CH6_LANES, new_cost, trials,
-                         status);
-}
-
-template <int NJ, int NU>
-__global__ __launch_bounds__(CH6_WG) void chain_iter_forward32_task_kernel(ChainK<double, NJ> P, ChainTaskK C,
-                                                                          int B, int T, ChainIter<double> a,
-                                                                          const int32_t* __restrict__ bstatus,
-                                                                          LSParams ls) {
-  __shared__ ChainK<double, NJ> Ps;
-  __shared__ double stage[(CH6_WG / CH6_LANES) * CH6_STAGE];
-  chain_consts_to_lds<CH6_WG>(Ps, P);
-  const int b = (blockIdx.x * CH6_WG + threadIdx.x) / CH6_LANES;
-  if (b >= B || a.status[b] != ILQR_TRAJ_OK) return;  // the whole lane group
-  const int l32 = threadIdx.x & (CH6_LANES - 1);
-  if (bstatus[b] != ILQR_TRAJ_OK) {  // as chain_iter_forward32_kernel
-    if (l32 == 0) {
-      a.status[b] = ILQR_TRAJ_NAN;
-      if (a.res_parity) a.res_parity[b] = a.parity;
-    }
-    return;
-  }
-  double du2 = 0.0;
-  const double pc = a.prev_cost ? a.prev_cost[b] : (double)INFINITY;
-  const ChainFwdOut<double> r =
-      chain_forward_group32<NJ, NU, true>(Ps, stage + (threadIdx.x / CH6_LANES) * CH6_STAGE, b, T, a.x, a.u,
-                                          a.xtraj, a.d, a.K, pc, a.xnew, a.unew, &du2, ls, C);
+  const ChainFwdOut<double> r = chain_forward_group32<NJ, NU, sizeof...(TaskK) == 1>(
+      Ps, stage + (threadIdx.x / CH6_LANES) * CH6_STAGE, b, T, a.x, a.u, a.xtraj, a.d, a.K, pc, a.xnew, a.unew, &du2,
+      ls, C...);
   if (l32 != 0) return;
   fwd_iter_finish(a, b, r.cost, r.accepted, r.trials, du2, ls.tol);
 }
@@ -2622,22 +2337,7 @@ struct ilqr_chain_handle {
   double *tA = nullptr, *tB = nullptr, *lx = nullptr, *lu = nullptr, *lxx = nullptr, *luu = nullptr;
   double *lfx = nullptr, *lfxx = nullptr;
   int32_t* bstatus = nullptr;
-  void* prev_cost = nullptr;
-  void* du2 = nullptr;
-  int32_t* trials = nullptr;
-  int32_t* status = nullptr;
-  int32_t* res_parity = nullptr;
-  int32_t* iters = nullptr;
-  // the fit driver's host-mapped words ([0], [1] running counts of the poll, [2] the
-  // call status tagged with the fit's number), their device alias, the gather's device
-  // call-status word, the poll's events
-  int32_t* host_words = nullptr;
-  ilqr::HostWait host_wait;  // the end-of-fit wait (wait_host_seq)
-  ilqr::HostWait poll_wait;  // the per-iteration convergence polls (wait_event)
-  int32_t* dev_words = nullptr;
-  int32_t* dev_flags = nullptr;
-  hipEvent_t ev_poll[2] = {nullptr, nullptr};
-  uint32_t fit_seq = 0;
+  ilqr::FitState fit;  // the fit driver's per-trajectory state, words and events (ilqr_fit.h)
   // closed-form dynamics of 2-joint chains (ilqr_chain_set_dynamics): available once
   // sampled and checked against the recursion at creation, used unless RNEA is asked for
   bool trig_ok = false;
@@ -2889,7 +2589,10 @@ hipError_t with_lin(const ilqr_chain_handle* h, Fn&& fn) {
 
 size_t vsize(const ilqr_chain_handle* h) { return h->dtype == ILQR_F32 ? 4 : 8; }
 
-// Typed operations of one (V, NJ, NU) instantiation.
+// Typed operations of one (V, NJ, NU) instantiation. The iteration's parts (linearize,
+// backward, forward, iteration) exist for two joints only: the recursion is
+// chain_backward4's, four 4 × 4 trajectories per wave. Another joint count answers
+// `dynamics` alone (six joints iterate through Chain6Ops).
 template <class V, int NJ, int NU>
 struct ChainOps {
   static constexpr int NX = 2 * NJ;
@@ -2897,18 +2600,17 @@ struct ChainOps {
   using Iter = ilqr::ChainIter<V>;
 
   static hipError_t linearize(ilqr_chain_handle* h, const V* x, const V* u, const int32_t* st) {
+    static_assert(NJ == 2, "ChainOps iterates 2-joint chains only");
     const auto P = chain_consts<V, NJ>(h->chain);
     const size_t lanes = (size_t)h->batch * h->T * (NX + NU);
     const dim3 grid((unsigned)((lanes + 255) / 256));
-    if constexpr (NJ == 2) {
-      if (h->use_trig()) {
-        const auto Q = trig_consts<V>(h);
-        return with_lin(h, [&](auto lin) {
-          ilqr::chain_linearize_kernel<V, NJ, NU, decltype(lin)::value, ilqr::ChainTrig<V>>
-              <<<grid, 256, 0, h->stream>>>(Q, h->batch, h->T, x, u, st, (V*)h->J);
-          return hipGetLastError();
-        });
-      }
+    if (h->use_trig()) {
+      const auto Q = trig_consts<V>(h);
+      return with_lin(h, [&](auto lin) {
+        ilqr::chain_linearize_kernel<V, NJ, NU, decltype(lin)::value, ilqr::ChainTrig<V>>
+            <<<grid, 256, 0, h->stream>>>(Q, h->batch, h->T, x, u, st, (V*)h->J);
+        return hipGetLastError();
+      });
     }
     return with_lin(h, [&](auto lin) {
       ilqr::chain_linearize_kernel<V, NJ, NU, decltype(lin)::value>
@@ -2929,34 +2631,29 @@ struct ChainOps {
   }
   static hipError_t backward(ilqr_chain_handle* h, const V* x, const V* u, V* d, V* K,
                              int32_t* st, double mu) {
+    static_assert(NJ == 2, "ChainOps iterates 2-joint chains only");
     hipError_t e = linearize(h, x, u, nullptr);
     if (e != hipSuccess) return e;
     const auto P = chain_consts<V, NJ>(h->chain);
-    if constexpr (NJ == 2) {  // four trajectories per wave on the f64 MFMA
-      ilqr::chain_backward4_kernel<V, NU><<<(h->batch + 15) / 16, 256, 0, h->stream>>>(
-          P, h->batch, h->T, x, (const V*)h->J, d, K, st, (V)mu, h->task());
-      return hipGetLastError();
-    }
-    ilqr::chain_backward_kernel<V, NJ, NU><<<(h->batch + ilqr::CH_WG - 1) / ilqr::CH_WG, ilqr::CH_WG,
-                                             0, h->stream>>>(P, h->batch, h->T, x, (const V*)h->J,
-                                                             d, K, st, (V)mu);
+    // four trajectories per wave on the f64 MFMA
+    ilqr::chain_backward4_kernel<V, NU><<<(h->batch + 15) / 16, 256, 0, h->stream>>>(
+        P, h->batch, h->T, x, (const V*)h->J, d, K, st, (V)mu, h->task());
     return hipGetLastError();
   }
   static hipError_t forward(ilqr_chain_handle* h, const V* x, const V* u, const V* xt, const V* d,
                             const V* K, const V* pc, V* xn, V* un, V* nc, int32_t* tr,
                             int32_t* st, const ilqr::LSParams& ls) {
-    if constexpr (NJ == 2) {
-      if (h->use_trig()) {
-        if (!ilqr::fg_fits<V>(h->T)) return hipErrorInvalidValue;
-        const auto Q = trig_consts<V>(h);
-        const int B = h->batch;
-        return ilqr::fg_with_lanes(B, false, [&](auto g) {
-          using G = decltype(g);
-          ilqr::chain_forward_trig_kernel<V, NU, G::L, G::W><<<G::blocks(B), G::threads, 0, h->stream>>>(
-              Q, B, h->T, x, u, xt, d, K, pc, xn, un, nc, tr, st, ls);
-          return hipGetLastError();
-        });
-      }
+    static_assert(NJ == 2, "ChainOps iterates 2-joint chains only");
+    if (h->use_trig()) {
+      if (!ilqr::fg_fits<V>(h->T)) return hipErrorInvalidValue;
+      const auto Q = trig_consts<V>(h);
+      const int B = h->batch;
+      return ilqr::fg_with_lanes(B, false, [&](auto g) {
+        using G = decltype(g);
+        ilqr::chain_forward_trig_kernel<V, NU, G::L, G::W><<<G::blocks(B), G::threads, 0, h->stream>>>(
+            Q, B, h->T, x, u, xt, d, K, pc, xn, un, nc, tr, st, ls);
+        return hipGetLastError();
+      });
     }
     const auto P = chain_consts<V, NJ>(h->chain);
     ilqr::chain_forward_kernel<V, NJ, NU><<<(h->batch * ilqr::CH_FW_LANES + ilqr::CH_WG - 1) / ilqr::CH_WG, ilqr::CH_WG,
@@ -2965,31 +2662,23 @@ struct ChainOps {
     return hipGetLastError();
   }
   static hipError_t iteration(ilqr_chain_handle* h, const Iter& a, const ilqr::LSParams& ls) {
+    static_assert(NJ == 2, "ChainOps iterates 2-joint chains only");
     hipError_t e = linearize(h, a.x, a.u, a.status);
     if (e != hipSuccess) return e;
     const auto P = chain_consts<V, NJ>(h->chain);
-    if constexpr (NJ == 2) {
-      ilqr::chain_iter_backward4_kernel<V, NU>
-          <<<(h->batch + 15) / 16, 256, 0, h->stream>>>(P, h->batch, h->T, a, (const V*)h->J, (V)ls.mu,
-                                                         h->task());
-    } else {
-      const int g = (h->batch + ilqr::CH_WG - 1) / ilqr::CH_WG;
-      ilqr::chain_iter_backward_kernel<V, NJ, NU>
-          <<<g, ilqr::CH_WG, 0, h->stream>>>(P, h->batch, h->T, a, (const V*)h->J, (V)ls.mu);
-    }
+    ilqr::chain_iter_backward4_kernel<V, NU>
+        <<<(h->batch + 15) / 16, 256, 0, h->stream>>>(P, h->batch, h->T, a, (const V*)h->J, (V)ls.mu, h->task());
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if constexpr (NJ == 2) {
-      if (h->use_trig()) {
-        if (!ilqr::fg_fits<V>(h->T)) return hipErrorInvalidValue;
-        const auto Q = trig_consts<V>(h);
-        const int B = h->batch;
-        return ilqr::fg_with_lanes(B, a.iter >= 2, [&](auto g) {  // wide: a fit past its first iteration
-          using G = decltype(g);
-          ilqr::chain_iter_forward_trig_kernel<V, NU, G::L, G::W>
-              <<<G::blocks(B), G::threads, 0, h->stream>>>(Q, B, h->T, a, ls);
-          return hipGetLastError();
-        });
-      }
+    if (h->use_trig()) {
+      if (!ilqr::fg_fits<V>(h->T)) return hipErrorInvalidValue;
+      const auto Q = trig_consts<V>(h);
+      const int B = h->batch;
+      return ilqr::fg_with_lanes(B, a.iter >= 2, [&](auto g) {  // wide: a fit past its first iteration
+        using G = decltype(g);
+        ilqr::chain_iter_forward_trig_kernel<V, NU, G::L, G::W>
+            <<<G::blocks(B), G::threads, 0, h->stream>>>(Q, B, h->T, a, ls);
+        return hipGetLastError();
+      });
     }
     const int gf = (h->batch * ilqr::CH_FW_LANES + ilqr::CH_WG - 1) / ilqr::CH_WG;
     ilqr::chain_iter_forward_kernel<V, NJ, NU><<<gf, ilqr::CH_WG, 0, h->stream>>>(P, h->batch, h->T,
@@ -3087,7 +2776,7 @@ struct Chain6Ops {
     const auto P = chain_consts<V, NJ>(h->chain);
     const int grid = (h->batch * ilqr::CH6_LANES + ilqr::CH6_WG - 1) / ilqr::CH6_WG;
     if (h->task_mode())
-      ilqr::chain_forward32_task_kernel<NJ, NU><<<grid, ilqr::CH6_WG, 0, h->stream>>>(
+      ilqr::chain_forward32_kernel<NJ, NU, ilqr::ChainTaskK><<<grid, ilqr::CH6_WG, 0, h->stream>>>(
           P, h->task6, h->batch, h->T, x, u, xt, d, K, pc, xn, un, nc, tr, st, ls);
     else
       ilqr::chain_forward32_kernel<NJ, NU><<<grid, ilqr::CH6_WG, 0, h->stream>>>(P, h->batch, h->T, x, u, xt, d, K,
@@ -3105,7 +2794,7 @@ struct Chain6Ops {
     const auto P = chain_consts<V, NJ>(h->chain);
     const int grid = (h->batch * ilqr::CH6_LANES + ilqr::CH6_WG - 1) / ilqr::CH6_WG;
     if (h->task_mode())
-      ilqr::chain_iter_forward32_task_kernel<NJ, NU><<<grid, ilqr::CH6_WG, 0, h->stream>>>(
+      ilqr::chain_iter_forward32_kernel<NJ, NU, ilqr::ChainTaskK><<<grid, ilqr::CH6_WG, 0, h->stream>>>(
           P, h->task6, h->batch, h->T, a, h->bstatus, ls);
     else
       ilqr::chain_iter_forward32_kernel<NJ, NU><<<grid, ilqr::CH6_WG, 0, h->stream>>>(P, h->batch, h->T, a,
@@ -3169,79 +2858,57 @@ template <class V>
 ilqr_status chain_fit_t(ilqr_chain_handle* h, const ilqr_options* o, const void* x_init,
                         const void* u_init, const void* x_traj, void* x_out, void* u_out,
                         void* cost, int32_t* iters, int32_t* status, const ilqr_history* hist) {
-  // The LQ fit driver's structure (ilqr_abi.cpp ilqr_fit_ex, DESIGN.md §4 fit driver):
-  // iteration 1 reads x_init / u_init in place (no copy-in), the last iteration writes
-  // x_out / u_out directly unless they overlap an input, a tol ≥ 0 fit stops enqueueing
-  // once every trajectory has stopped (the running count one iteration behind), and the
-  // call ends with one gather + a one-thread launch that publishes the call status to a
-  // host-mapped word the host spins on (no status copy, no host fold).
-  const size_t B = (size_t)h->batch, nx = 2 * (size_t)h->nj;
-  const size_t nxe = (h->T + 1) * nx, nue = (size_t)h->T * h->nu;
+  // The shared fit driver (ilqr_fit.h, DESIGN.md §4 fit driver) around this family's iteration
   hipStream_t s = h->stream;
+  ilqr::FitState& f = h->fit;
   const ilqr::LSParams ls = ilqr::ls_params(o);
-  const int max_iter = o ? o->max_iter : 100;
-  const unsigned g = (unsigned)((B + 255) / 256);
-  ilqr::chain_fit_init_kernel<V><<<g, 256, 0, s>>>(h->batch, (V*)h->prev_cost, h->status, h->res_parity, h->iters);
-  CH_TRY(hipGetLastError());
-  volatile int32_t* flags = h->host_words + 2;
-  *flags = 0;
-  const size_t xb = sizeof(V) * B * nxe, ub = sizeof(V) * B * nue;
-  auto overlap = [](const void* p, size_t np, const void* q, size_t nq) {
-    const char *a = (const char*)p, *b = (const char*)q;
-    return q && a < b + nq && b < a + np;
-  };
-  const bool direct = max_iter > 0 && !overlap(x_out, xb, x_init, xb) && !overlap(x_out, xb, x_traj, xb) &&
-                      !overlap(x_out, xb, u_init, ub) && !overlap(u_out, ub, u_init, ub) &&
-                      !overlap(u_out, ub, x_init, xb) && !overlap(u_out, ub, x_traj, xb);
-  const bool poll = ls.tol >= 0.0 && max_iter > 2;
-  int enqueued = 0, waited = 0;  // iterations (the end-of-fit wait's units)
-  for (int it = 1; it <= max_iter; ++it) {  // forward_pass.jl:161
-    const int par = (it - 1) & 1;
-    const bool last = direct && it == max_iter;
-    auto a = iter_args<V>(h, it == 1 ? x_init : h->xbuf[par], it == 1 ? u_init : h->ubuf[par], x_traj,
-                          last ? x_out : h->xbuf[par ^ 1], last ? u_out : h->ubuf[par ^ 1], h->prev_cost,
-                          h->prev_cost, h->du2, h->trials, h->status);
-    a.res_parity = h->res_parity;
-    a.iters = h->iters;
-    a.parity = it == 1 ? ilqr::PARITY_INPUT : par;  // where the input x̄ⁱ, ūⁱ lie (:174-175)
+  ilqr::FitCall c;
+  c.B = h->batch, c.T = h->T, c.nx = 2 * h->nj, c.nu = h->nu;
+  c.f32 = sizeof(V) == 4;
+  c.max_iter = o ? o->max_iter : 100;
+  c.x_init = x_init, c.u_init = u_init, c.x_out = x_out, c.u_out = u_out;
+  for (int i = 0; i < 2; ++i) c.xbuf[i] = h->xbuf[i], c.ubuf[i] = h->ubuf[i];
+  CH_TRY(ilqr::fit_begin(f, c, x_traj, ls.tol, /*init=*/true, s));
+  for (int it = 1; it <= c.max_iter; ++it) {  // forward_pass.jl:161
+    const ilqr::FitBuffers b = ilqr::fit_buffers(c, it);
+    auto a = iter_args<V>(h, b.x, b.u, x_traj, b.xnew, b.unew, f.prev_cost, f.prev_cost, f.du2, f.trials, f.status);
+    a.res_parity = f.res_parity;
+    a.iters = f.iters;
+    a.parity = b.parity;
     a.iter = it;
     CH_TRY(dispatch<V>(h, [&](auto ops) { return decltype(ops)::iteration(h, a, ls); }));
-    enqueued = it;
     if (hist)  // the per-iteration record (ilqr_history)
-      CH_TRY(ilqr::launch_record_history(h->batch, it, h->status, h->iters, h->trials, h->prev_cost, h->du2,
-                                         sizeof(V) == 4, ls.alpha0, ls.shrink, hist->cost, hist->trials,
-                                         hist->alpha, hist->du2, s));
-    if (!poll || it == max_iter) continue;
-    CH_TRY(ilqr::launch_count_running(h->batch, h->status, h->dev_words + (it & 1), s));
-    CH_TRY(hipEventRecord(h->ev_poll[it & 1], s));
-    if (it >= 2) {  // iteration it−1's count, read while iteration it runs (:171's break)
-      CH_TRY(ilqr::wait_event(h->ev_poll[(it - 1) & 1], &h->poll_wait));
-      waited = it - 1;
-      if (__atomic_load_n(h->host_words + ((it - 1) & 1), __ATOMIC_ACQUIRE) == 0) break;
-    }
+      CH_TRY(ilqr::launch_record_history(h->batch, it, f.status, f.iters, f.trials, f.prev_cost, f.du2, c.f32,
+                                         ls.alpha0, ls.shrink, hist->cost, hist->trials, hist->alpha, hist->du2,
+                                         s));
+    bool stopped;
+    CH_TRY(ilqr::fit_poll(f, c, it, s, &stopped));
+    if (stopped) break;
   }
-  // still-running trajectories (max_iter reached) return the last accepted iterate
-  const int final_parity =
-      max_iter == 0 ? ilqr::PARITY_INPUT : (direct ? ilqr::PARITY_OUT : (max_iter & 1));
-  ilqr::chain_gather_kernel<V><<<dim3(1, h->batch), 256, 0, s>>>(
-      h->batch, (int)nxe, (int)nue, (const V*)x_init, (const V*)u_init, (const V*)h->xbuf[0],
-      (const V*)h->ubuf[0], (const V*)h->xbuf[1], (const V*)h->ubuf[1], h->res_parity, h->status, final_parity,
-      (const V*)h->prev_cost, h->iters, (V*)x_out, (V*)u_out, (V*)cost, iters, status, h->dev_flags);
-  CH_TRY(hipGetLastError());
-  uint32_t seq = (++h->fit_seq) & 0x3fffffffu;
-  if (seq == 0) seq = h->fit_seq = 1;  // 0 is the word's cleared value
-  CH_TRY(ilqr::launch_publish_flags(h->dev_flags, h->dev_words + 2, seq, s));
-  CH_TRY(ilqr::wait_host_seq(h->host_words + 2, seq, enqueued - waited, s, &h->host_wait));
-  const int32_t f = __atomic_load_n(h->host_words + 2, __ATOMIC_ACQUIRE);
-  return (f & 1) ? ILQR_ERR_NAN : ((f & 2) ? ILQR_ERR_LS_EXHAUSTED : ILQR_OK);
+  ilqr_status st = ILQR_OK;
+  CH_TRY(ilqr::fit_end(f, c, cost, iters, status, s, &st));
+  return st;
 }
 
-// A six-joint handle's cost mode: the weights the per-step tiles and the forward read
-// (ℓ = Σu² in a task mode: q = 0, r = 1, qf = 0; the handle's own in the joint mode) and the
-// Hessian tiles that go with them, enqueued on the handle's stream as at creation.
-// h->task6 is set by the caller.
-ilqr_status chain6_set_cost_mode(ilqr_chain_handle* h, int32_t mode) {
-  CH_TRY(hipSetDevice(h->device));
+// The argument check of the two cost entries (ilqr_chain_set_simple_costs, _set_task_costs):
+// the mode, and what a task mode reads
+ilqr_status check_cost_args(const ilqr_chain_handle* h, int32_t mode, int32_t body, const double* point,
+                            const double* final_target, double weight) {
+  if (mode != ILQR_CHAIN_COST_JOINT && mode != ILQR_CHAIN_COST_SIMPLE &&
+      mode != ILQR_CHAIN_COST_SIMPLE_EUCLIDEAN)
+    return ILQR_ERR_BAD_ARG;
+  if (mode == ILQR_CHAIN_COST_JOINT) return ILQR_OK;  // the joint-space costs: nothing else is read
+  if (!point || !final_target || !std::isfinite(weight)) return ILQR_ERR_BAD_ARG;
+  if (body < -1 || body >= h->nj) return ILQR_ERR_BAD_ARG;
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(point[k]) || !std::isfinite(final_target[k])) return ILQR_ERR_BAD_ARG;
+  return ILQR_OK;
+}
+
+// The weights the kernels read in cost mode `mode`: the handle's own as created in the joint
+// mode, ℓ = Σu² in a task mode (simple_immediate_cost, cost_functions.jl:45-51: q = 0, r = 1,
+// qf = 0). The caller has made sure no launch in flight still reads the old ones.
+void apply_cost_mode(ilqr_chain_handle* h, int32_t mode) {
   h->chain = h->created;
   if (mode != ILQR_CHAIN_COST_JOINT)
     for (int i = 0; i < ILQR_CHAIN_MAX_JOINTS; ++i) {
@@ -3250,6 +2917,14 @@ ilqr_status chain6_set_cost_mode(ilqr_chain_handle* h, int32_t mode) {
       h->chain.qf_weight[i] = 0.0;
     }
   h->cost_mode = mode;
+}
+
+// A six-joint handle's cost mode: the weights the per-step tiles and the forward read and the
+// Hessian tiles that go with them, enqueued on the handle's stream as at creation (launches
+// take the weights by value, in stream order). h->task6 is set by the caller.
+ilqr_status chain6_set_cost_mode(ilqr_chain_handle* h, int32_t mode) {
+  CH_TRY(hipSetDevice(h->device));
+  apply_cost_mode(h, mode);
   CH_TRY(Chain6Ops::hessians(h));
   return ILQR_OK;
 }
@@ -3320,18 +2995,7 @@ ilqr_status ilqr_chain_create(ilqr_chain_handle** out, int device, const ilqr_ch
       if (e == hipSuccess) e = hipMemset(h->lu, 0, sizeof(double) * B * T * nu);
       if (e == hipSuccess) e = hipMemset(h->lfx, 0, sizeof(double) * B * nx);
     }
-    if (e == hipSuccess) e = hipMalloc(&h->prev_cost, w * B);
-    if (e == hipSuccess) e = hipMalloc(&h->du2, w * B);
-    if (e == hipSuccess) e = hipMalloc(&h->trials, sizeof(int32_t) * B);
-    if (e == hipSuccess) e = hipMalloc(&h->status, sizeof(int32_t) * B);
-    if (e == hipSuccess) e = hipMalloc(&h->res_parity, sizeof(int32_t) * B);
-    if (e == hipSuccess) e = hipMalloc(&h->iters, sizeof(int32_t) * B);
-    if (e == hipSuccess)
-      e = hipHostMalloc(&h->host_words, sizeof(int32_t) * 4, hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&h->dev_words, h->host_words, 0);
-    if (e == hipSuccess) e = hipMalloc(&h->dev_flags, sizeof(int32_t) * 2);
-    if (e == hipSuccess) e = hipMemset(h->dev_flags, 0, sizeof(int32_t) * 2);
-    for (int c = 0; c < 2 && e == hipSuccess; ++c) e = hipEventCreateWithFlags(&h->ev_poll[c], hipEventDisableTiming);
+    if (e == hipSuccess) e = ilqr::fit_state_create(&h->fit, B, w);
   }
   if (e != hipSuccess) {
     ilqr_chain_destroy(h);
@@ -3370,22 +3034,16 @@ ilqr_status ilqr_chain_set_simple_costs(ilqr_chain_handle* h, int32_t mode, int3
                                         const double* point, const double* final_target,
                                         double weight) {
   if (!h) return ILQR_ERR_BAD_ARG;
-  if (mode != ILQR_CHAIN_COST_JOINT && mode != ILQR_CHAIN_COST_SIMPLE &&
-      mode != ILQR_CHAIN_COST_SIMPLE_EUCLIDEAN)
-    return ILQR_ERR_BAD_ARG;
+  const ilqr_status st = check_cost_args(h, mode, body, point, final_target, weight);
+  if (st != ILQR_OK) return st;
   if (mode == ILQR_CHAIN_COST_JOINT) {  // the joint-space costs the handle was created with
     if (h->cost_mode != ILQR_CHAIN_COST_JOINT) {
       if (h->nj == 6) return chain6_set_cost_mode(h, ILQR_CHAIN_COST_JOINT);  // its tiles too
       CH_TRY(hipStreamSynchronize(h->stream));  // launches in flight still read the old cost
-      h->chain = h->created;
-      h->cost_mode = ILQR_CHAIN_COST_JOINT;
+      apply_cost_mode(h, ILQR_CHAIN_COST_JOINT);
     }
     return ILQR_OK;
   }
-  if (!point || !final_target || !std::isfinite(weight)) return ILQR_ERR_BAD_ARG;
-  if (body < -1 || body >= h->nj) return ILQR_ERR_BAD_ARG;
-  for (int k = 0; k < 3; ++k)
-    if (!std::isfinite(point[k]) || !std::isfinite(final_target[k])) return ILQR_ERR_BAD_ARG;
   if (!iter_supported(h->nj, h->nu) || !h->use_trig()) {
     g_chain_error = "ilqr_chain_set_simple_costs: needs a 2-joint chain on the closed-form dynamics";
     return ILQR_ERR_UNSUPPORTED;
@@ -3402,14 +3060,7 @@ ilqr_status ilqr_chain_set_simple_costs(ilqr_chain_handle* h, int32_t mode, int3
   CH_TRY(hipStreamSynchronize(h->stream));
   if (!h->task_dev) CH_TRY(hipMalloc(&h->task_dev, sizeof(ilqr::ChainTask)));
   CH_TRY(hipMemcpy(h->task_dev, &C, sizeof(C), hipMemcpyHostToDevice));
-  // simple_immediate_cost = Σ uᵢ² (cost_functions.jl:45-51): q_weight 0, r_weight 1
-  h->chain = h->created;
-  for (int i = 0; i < ILQR_CHAIN_MAX_JOINTS; ++i) {
-    h->chain.q_weight[i] = 0.0;
-    h->chain.r_weight[i] = 1.0;
-    h->chain.qf_weight[i] = 0.0;
-  }
-  h->cost_mode = mode;
+  apply_cost_mode(h, mode);
   return ILQR_OK;
 }
 
@@ -3418,15 +3069,10 @@ ilqr_status ilqr_chain_set_task_costs(ilqr_chain_handle* h, int32_t mode, int32_
   if (!h) return ILQR_ERR_BAD_ARG;
   // 2-joint chains: the sampled closed form, with its returns
   if (iter_supported(h->nj, h->nu)) return ilqr_chain_set_simple_costs(h, mode, body, point, final_target, weight);
-  if (mode != ILQR_CHAIN_COST_JOINT && mode != ILQR_CHAIN_COST_SIMPLE &&
-      mode != ILQR_CHAIN_COST_SIMPLE_EUCLIDEAN)
-    return ILQR_ERR_BAD_ARG;
+  const ilqr_status st = check_cost_args(h, mode, body, point, final_target, weight);
+  if (st != ILQR_OK) return st;
   if (mode == ILQR_CHAIN_COST_JOINT)
     return h->cost_mode == ILQR_CHAIN_COST_JOINT ? ILQR_OK : chain6_set_cost_mode(h, ILQR_CHAIN_COST_JOINT);
-  if (!point || !final_target || !std::isfinite(weight)) return ILQR_ERR_BAD_ARG;
-  if (body < -1 || body >= h->nj) return ILQR_ERR_BAD_ARG;
-  for (int k = 0; k < 3; ++k)
-    if (!std::isfinite(point[k]) || !std::isfinite(final_target[k])) return ILQR_ERR_BAD_ARG;
   if (h->nj != 6 || !handle_iterates(h)) {
     g_chain_error = "ilqr_chain_set_task_costs: needs a handle that iterates on the tiles path (six joints, fp64)";
     return ILQR_ERR_UNSUPPORTED;
@@ -3468,13 +3114,10 @@ ilqr_status ilqr_chain_destroy(ilqr_chain_handle* h) {
     (void)hipFree(h->xbuf[i]);
     (void)hipFree(h->ubuf[i]);
   }
-  for (void* p : {h->K, h->d, h->J, h->prev_cost, h->du2}) (void)hipFree(p);
+  for (void* p : {h->K, h->d, h->J}) (void)hipFree(p);
   for (double* p : {h->tA, h->tB, h->lx, h->lu, h->lxx, h->luu, h->lfx, h->lfxx}) (void)hipFree(p);
   (void)hipFree(h->bstatus);
-  for (int32_t* p : {h->trials, h->status, h->res_parity, h->iters, h->dev_flags}) (void)hipFree(p);
-  if (h->host_words) (void)hipHostFree(h->host_words);
-  for (hipEvent_t ev : h->ev_poll)
-    if (ev) (void)hipEventDestroy(ev);
+  ilqr::fit_state_destroy(&h->fit);
   (void)hipFree(h->task_dev);
   delete h;
   return ILQR_OK;

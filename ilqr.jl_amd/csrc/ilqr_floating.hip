@@ -1429,17 +1429,6 @@ __global__ void fb_finish_kernel(int B, int32_t* __restrict__ status, int32_t* _
   if (status[b] == ILQR_TRAJ_LS_EXHAUSTED) atomicOr(flags, 2);
 }
 
-__global__ void fb_count_kernel(int B, const int32_t* __restrict__ status, int32_t* __restrict__ out) {
-  __shared__ int n;
-  if (threadIdx.x == 0) n = 0;
-  __syncthreads();
-  int k = 0;
-  for (int b = threadIdx.x; b < B; b += blockDim.x) k += status[b] == ILQR_TRAJ_OK;
-  atomicAdd(&n, k);
-  __syncthreads();
-  if (threadIdx.x == 0) *out = n;
-}
-
 }  // namespace
 }  // namespace ilqr
 
@@ -1803,8 +1792,7 @@ ilqr_status ilqr_floating_fit_ex(ilqr_floating_handle* h, const ilqr_options* o,
       FB_TRY(ilqr::launch_record_history(B, it, h->status, h->iters, h->trials, h->prev_cost, h->du2, false,
                                          ls.alpha0, ls.shrink, hist->cost, hist->trials, hist->alpha, hist->du2, s));
     if (ls.tol >= 0.0 && it < max_iter) {  // :171's break once every trajectory stopped
-      ilqr::fb_count_kernel<<<1, 256, 0, s>>>(B, h->status, h->words);
-      FB_TRY(hipGetLastError());
+      FB_TRY(ilqr::launch_count_running(B, h->status, h->words, s));
       int32_t running = 0;
       FB_TRY(hipMemcpyAsync(&running, h->words, 4, hipMemcpyDeviceToHost, s));
       FB_TRY(hipStreamSynchronize(s));
@@ -1821,7 +1809,7 @@ ilqr_status ilqr_floating_fit_ex(ilqr_floating_handle* h, const ilqr_options* o,
   int32_t flags = 0;
   FB_TRY(hipMemcpyAsync(&flags, h->words + 1, 4, hipMemcpyDeviceToHost, s));
   FB_TRY(hipStreamSynchronize(s));
-  return (flags & 1) ? ILQR_ERR_NAN : ((flags & 2) ? ILQR_ERR_LS_EXHAUSTED : ILQR_OK);
+  return ilqr::call_status(flags);
 }
 
 }  // extern "C"

@@ -152,19 +152,24 @@ constexpr int PARITY_INPUT = 2;
 // that stopped earlier)
 constexpr int PARITY_OUT = 3;
 // fit's per-trajectory state: prev_cost = +Inf, status OK, res_parity INPUT, iters 0.
-hipError_t launch_fit_init(int B, double* prev_cost, int32_t* status, int32_t* res_parity,
+// `f32`: prev_cost is float (the chain family in fp32), as in launch_record_history.
+hipError_t launch_fit_init(int B, void* prev_cost, bool f32, int32_t* status, int32_t* res_parity,
                            int32_t* iters, hipStream_t s);
 // x_out[b] = the buffer res_parity[b] names (final_parity for still-running ones,
 // whose status becomes MAX_ITER), and u; cost/iters/status copied out (each may be
 // null). The call-status bits go through dflags (two zeroed device words, re-armed by
-// the kernel) into `flags` (host-mapped, may be null) as (seq << 2) | bits.
-hipError_t launch_gather_result(int B, int T, int nx, int nu, const double* xin, const double* uin,
-                                const double* x0, const double* u0, const double* x1,
-                                const double* u1, const int32_t* res_parity, int32_t* status,
-                                int final_parity, const double* fit_cost, const int32_t* fit_iters,
-                                double* x_out, double* u_out, double* cost_out,
-                                int32_t* iters_out, int32_t* status_out, int32_t* dflags,
+// the kernel) into `flags` (host-mapped, may be null) as (seq << 2) | bits by the fit's
+// last launch (gather_flags_kernel). `f32`: the trajectories and costs are float.
+hipError_t launch_gather_result(int B, int T, int nx, int nu, bool f32, const void* xin, const void* uin,
+                                const void* x0, const void* u0, const void* x1, const void* u1,
+                                const int32_t* res_parity, int32_t* status, int final_parity,
+                                const void* fit_cost, const int32_t* fit_iters, void* x_out, void* u_out,
+                                void* cost_out, int32_t* iters_out, int32_t* status_out, int32_t* dflags,
                                 int32_t* flags, hipStream_t s, uint32_t seq = 0);
+// the call status those bits stand for
+inline ilqr_status call_status(int32_t flags) {
+  return (flags & 1) ? ILQR_ERR_NAN : ((flags & 2) ? ILQR_ERR_LS_EXHAUSTED : ILQR_OK);
+}
 // (N, R, C) row-major → (N, R2, C2) zero-padded (R2 ≥ R, C2 ≥ C), and back.
 hipError_t launch_pad3(const double* src, double* dst, size_t N, int R, int C, int R2, int C2,
                        hipStream_t s);
@@ -188,9 +193,6 @@ hipError_t launch_lq_linearize(int nx, int nu, const LQParams& p, int B, int T, 
                                hipStream_t s);
 // *out = #trajectories with status OK (out may be host-mapped memory)
 hipError_t launch_count_running(int B, const int32_t* status, int32_t* out, hipStream_t s);
-// The last launch of a fit (gather_flags_kernel): dflags[0] (a gather's call-status
-// bits, re-armed) into the host-mapped word `flags` as (seq << 2) | bits.
-hipError_t launch_publish_flags(int32_t* dflags, int32_t* flags, uint32_t seq, hipStream_t s);
 // The host's end of a fit: wait until the host-mapped word carries `seq` in bits 2..31,
 // `units` = the fit iterations the wait covers (the policy: ilqr_wait.h; ILQR_FIT_WAIT=sync
 // forces the stream sync). wait_event: the same for an event (the fit drivers' polls, one

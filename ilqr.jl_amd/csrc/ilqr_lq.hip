@@ -583,9 +583,10 @@ __global__ __launch_bounds__(256, 4) void lq_iter_pipe_kernel(LQParams P, int B,
 
 // dst[0, n) = src[0, n) by one wave: eight loads per lane in flight before their stores
 // (a load-store pair per element waits out the memory latency once per 64 elements)
-__device__ inline void wave_copy(double* __restrict__ dst, const double* __restrict__ src, int n, int l) {
+template <class V>
+__device__ inline void wave_copy(V* __restrict__ dst, const V* __restrict__ src, int n, int l) {
   for (int i0 = 0; i0 < n; i0 += 64 * 8) {
-    double v[8];
+    V v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int i = i0 + j * 64 + l;
@@ -606,15 +607,15 @@ __device__ inline void wave_copy(double* __restrict__ dst, const double* __restr
 // with one plain store and re-arms it — no device atomics on host memory (those need
 // PCIe AtomicOps). A last-block ticket in this kernel instead (a release fence and an
 // acq_rel agent-scope atomic per block: an L2 write-back each) cost 42 µs per fit at
-// B = 4096 against ≈2 µs for the second launch.
-__global__ __launch_bounds__(256) void gather_kernel(int B, int T, int nx, int nu, const double* xin,
-                                                     const double* uin, const double* x0, const double* u0,
-                                                     const double* x1, const double* u1,
+// B = 4096 against ≈2 µs for the second launch. V: the family's value type (the chain
+// family's fits are fp32 or fp64).
+template <class V>
+__global__ __launch_bounds__(256) void gather_kernel(int B, int T, int nx, int nu, const V* xin, const V* uin,
+                                                     const V* x0, const V* u0, const V* x1, const V* u1,
                                                      const int32_t* res_parity, int32_t* status,
-                                                     int final_parity, const double* fit_cost,
-                                                     const int32_t* fit_iters, double* x_out, double* u_out,
-                                                     double* cost_out, int32_t* iters_out,
-                                                     int32_t* status_out, int32_t* dflags) {
+                                                     int final_parity, const V* fit_cost,
+                                                     const int32_t* fit_iters, V* x_out, V* u_out, V* cost_out,
+                                                     int32_t* iters_out, int32_t* status_out, int32_t* dflags) {
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int l = threadIdx.x & 63;
   if (b < B) {
@@ -622,8 +623,8 @@ __global__ __launch_bounds__(256) void gather_kernel(int B, int T, int nx, int n
     const bool running = st0 == ILQR_TRAJ_OK;
     const int par = running ? final_parity : res_parity[b];
     if (par != PARITY_OUT) {  // PARITY_OUT: the last iteration wrote x_out / u_out itself
-      const double* xs = (par == PARITY_INPUT ? xin : (par ? x1 : x0)) + (size_t)b * (T + 1) * nx;
-      const double* us = (par == PARITY_INPUT ? uin : (par ? u1 : u0)) + (size_t)b * T * nu;
+      const V* xs = (par == PARITY_INPUT ? xin : (par ? x1 : x0)) + (size_t)b * (T + 1) * nx;
+      const V* us = (par == PARITY_INPUT ? uin : (par ? u1 : u0)) + (size_t)b * T * nu;
       wave_copy(x_out + (size_t)b * (T + 1) * nx, xs, (T + 1) * nx, l);
       wave_copy(u_out + (size_t)b * T * nu, us, T * nu, l);
     }
@@ -684,11 +685,11 @@ __global__ void record_history_kernel(int B, int stride, int it, const int32_t* 
   if (h_du2) h_du2[o] = ran ? (double)du2[b] : (double)NAN;
 }
 
-__global__ void fit_init_kernel(int B, double* prev_cost, int32_t* status, int32_t* res_parity,
-                                int32_t* iters) {
+template <class V>
+__global__ void fit_init_kernel(int B, V* prev_cost, int32_t* status, int32_t* res_parity, int32_t* iters) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  prev_cost[b] = INFINITY;
+  prev_cost[b] = V(INFINITY);
   status[b] = ILQR_TRAJ_OK;
   res_parity[b] = PARITY_INPUT;
   iters[b] = 0;
@@ -871,17 +872,22 @@ hipError_t launch_lq_iter_pipe(int nx, int nu, const LQParams& p, int B, int T, 
   return hipErrorInvalidValue;
 }
 
-hipError_t launch_gather_result(int B, int T, int nx, int nu, const double* xin, const double* uin,
-                                const double* x0, const double* u0, const double* x1,
-                                const double* u1, const int32_t* res_parity, int32_t* status,
-                                int final_parity, const double* fit_cost, const int32_t* fit_iters,
-                                double* x_out, double* u_out, double* cost_out,
-                                int32_t* iters_out, int32_t* status_out, int32_t* dflags,
+hipError_t launch_gather_result(int B, int T, int nx, int nu, bool f32, const void* xin, const void* uin,
+                                const void* x0, const void* u0, const void* x1, const void* u1,
+                                const int32_t* res_parity, int32_t* status, int final_parity,
+                                const void* fit_cost, const int32_t* fit_iters, void* x_out, void* u_out,
+                                void* cost_out, int32_t* iters_out, int32_t* status_out, int32_t* dflags,
                                 int32_t* flags, hipStream_t s, uint32_t seq) {
   if (B <= 0) return hipSuccess;
-  gather_kernel<<<(B + 3) / 4, 256, 0, s>>>(B, T, nx, nu, xin, uin, x0, u0, x1, u1, res_parity, status,
-                                            final_parity, fit_cost, fit_iters, x_out, u_out, cost_out,
-                                            iters_out, status_out, dflags);
+  auto gather = [&](auto v) {
+    using V = decltype(v);
+    gather_kernel<V><<<(B + 3) / 4, 256, 0, s>>>(
+        B, T, nx, nu, (const V*)xin, (const V*)uin, (const V*)x0, (const V*)u0, (const V*)x1, (const V*)u1,
+        res_parity, status, final_parity, (const V*)fit_cost, fit_iters, (V*)x_out, (V*)u_out, (V*)cost_out,
+        iters_out, status_out, dflags);
+  };
+  if (f32) gather(float{});
+  else gather(double{});
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   gather_flags_kernel<<<1, 1, 0, s>>>(dflags, flags, seq);
@@ -917,10 +923,12 @@ hipError_t launch_record_history(int B, int it, const int32_t* status, const int
   return hipGetLastError();
 }
 
-hipError_t launch_fit_init(int B, double* prev_cost, int32_t* status, int32_t* res_parity,
+hipError_t launch_fit_init(int B, void* prev_cost, bool f32, int32_t* status, int32_t* res_parity,
                            int32_t* iters, hipStream_t s) {
   if (B <= 0) return hipSuccess;
-  fit_init_kernel<<<(B + 255) / 256, 256, 0, s>>>(B, prev_cost, status, res_parity, iters);
+  const int g = (B + 255) / 256;
+  if (f32) fit_init_kernel<float><<<g, 256, 0, s>>>(B, (float*)prev_cost, status, res_parity, iters);
+  else fit_init_kernel<double><<<g, 256, 0, s>>>(B, (double*)prev_cost, status, res_parity, iters);
   return hipGetLastError();
 }
 
@@ -963,11 +971,6 @@ __global__ __launch_bounds__(256) void count_running_kernel(int B, const int32_t
   atomicAdd(&total, n);
   __syncthreads();
   if (threadIdx.x == 0) *out = total;
-}
-
-hipError_t launch_publish_flags(int32_t* dflags, int32_t* flags, uint32_t seq, hipStream_t s) {
-  gather_flags_kernel<<<1, 1, 0, s>>>(dflags, flags, seq);
-  return hipGetLastError();
 }
 
 hipError_t launch_count_running(int B, const int32_t* status, int32_t* out, hipStream_t s) {

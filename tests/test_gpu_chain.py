@@ -528,6 +528,41 @@ def test_chain_fit_equals_iterate_replay(gpu, g2, dtype, max_iter, tol, max_tria
         assert ref[4][1].item() == _lib.TRAJ_NAN
 
 
+def test_chain_fit_batch_past_grid_y_limit(gpu):
+    """A chain fit of 65,537 trajectories, more than a grid's y dimension holds (65,535): the
+    fit's gather indexes trajectories by blockIdx.x like every other kernel of the path (one
+    block per trajectory on dim3(1, batch) was refused at launch). In place (x_out = x_init,
+    u_out = u_init), so the gather copies every trajectory and none goes out directly; a NaN
+    in the last trajectory, so the far end of the batch is told apart. Equal to the same
+    iterations through ilqr_chain_iterate, bit for bit."""
+    import ctypes as C
+    nb, T, dtype = 65537, 3, torch.float64
+    rng = np.random.default_rng(65537)
+    x5 = np.concatenate([rng.uniform(-1, 1, (5, 2)), rng.uniform(-0.5, 0.5, (5, 2))], axis=1)
+    u5 = dev(rng.uniform(-0.5, 0.5, (5, T, 1)), dtype)  # five start patterns, tiled over the batch
+    x5 = ChainSolver(rbd_2dof_problem(1), T, 5, dtype=dtype, linearization="fd").rollout(dev(x5, dtype), u5)
+    rep = (nb + 4) // 5
+    x0 = x5.repeat(rep, 1, 1)[:nb].contiguous()
+    u0 = u5.repeat(rep, 1, 1)[:nb].contiguous()
+    x0[nb - 1, 1, 0] = float("nan")
+    s = ChainSolver(rbd_2dof_problem(1), T, nb, dtype=dtype, linearization="fd")
+    max_iter, tol = 2, -1.0
+    ref = chain_fit_replay(s, x0, u0, max_iter, tol, None)
+    xi, ui = x0.clone(), u0.clone()
+    cost = torch.empty((nb,), dtype=dtype, device="cuda")
+    it = torch.empty((nb,), dtype=torch.int32, device="cuda")
+    st = torch.empty((nb,), dtype=torch.int32, device="cuda")
+    s._bind()
+    o = _lib.default_options(max_iter=max_iter, tol=tol)
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    cs = s.lib.ilqr_chain_fit(s.h, C.byref(o), p(xi), p(ui), None, p(xi), p(ui), p(cost), p(it), p(st))
+    assert cs == ref[5] == _lib.ERR_NAN
+    for a, b in zip((xi, ui, cost, it), ref[:4]):
+        torch.testing.assert_close(a, b, rtol=0, atol=0, equal_nan=True)
+    assert torch.equal(st, ref[4])
+    assert st[nb - 1].item() == _lib.TRAJ_NAN
+
+
 # -- the rare ends of the line search (tests/forward_ends.py), per forward kernel ----------
 def _ends_case(dtype, nu):
     """B = 5, T = 7 (ragged against 4 trajectories per wave and 16 per workgroup): a
