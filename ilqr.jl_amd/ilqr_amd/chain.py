@@ -111,26 +111,77 @@ def rbd_2dof_problem(nu: int = 2) -> ChainProblem:
                         RBD_R_JOINT, RBD_QF_JOINT)
 
 
-def coupled_2dof_problem(nu: int = 2) -> ChainProblem:
+def coupled_2dof_problem(nu: int = 2, oblique: bool = False) -> ChainProblem:
     """A non-degenerate 2-joint chain for parity tests (not a reference robot): the
     2Dof_arm's joint layout with the first joint frame tilted, COMs off the joint
     origins, anisotropic inertias with products of inertia, and gravity on. Unlike the
     2Dof_arm (COMs on the joint axes, 0.5·I inertias, zero gravity: constant
     M = diag(4, 0.5), zero bias), M(q) is dense and q-dependent and the bias carries
-    Coriolis and gravity terms, so A's q-columns are nonzero."""
+    Coriolis and gravity terms, so A's q-columns are nonzero.
+
+    oblique=True also turns joint 2's frame about z (R0ᵀ ≠ R0), tilts its axis off the
+    principal directions and lifts its origin off the x axis: the rotation order of
+    R0·[a]×, the R0·a·aᵀ term and the y, z components of p enter (joint 2's frame, axis
+    and p_z are those of tests/closures.py coupled_floating_model; p_y is added)."""
     ch = load_robot("2dof_arm")
     c, s = math.cos(0.3), math.sin(0.3)
-    R0 = ch.R0.copy()
+    R0, p, axis = ch.R0.copy(), ch.p.copy(), ch.axis.copy()
     R0[0] = np.array([[1.0, 0.0, 0.0], [0.0, c, -s], [0.0, s, c]])   # joint 1 tilted about x
+    if oblique:
+        c, s = math.cos(0.2), math.sin(0.2)
+        R0[1] = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])   # joint 2 turned about z
+        axis[1] = np.array([0.0, 1.0, 0.2]) / math.sqrt(1.04)
+        p[1] = np.array([1.0, -0.15, 0.1])
     com = np.array([[0.10, 0.05, 0.20], [0.30, 0.05, -0.15]])
     Ic = np.array([[[0.40, 0.02, 0.01], [0.02, 0.60, 0.03], [0.01, 0.03, 0.30]],
                    [[0.20, 0.01, -0.02], [0.01, 0.35, 0.015], [-0.02, 0.015, 0.25]]])
-    chain = Chain(list(ch.names), R0, ch.p.copy(), ch.axis.copy(), np.array([3.0, 2.0]), com, Ic,
+    chain = Chain(list(ch.names), R0, p, axis, np.array([3.0, 2.0]), com, Ic,
                   np.array([0.0, 0.0, -9.81]))
     return ChainProblem(chain, nu, RBD_DT, RBD_TARGET_JOINTS, RBD_Q_JOINT, RBD_R_JOINT, RBD_QF_JOINT)
 
 
 RBD_TARGET_JOINTS_6DOF = (0.5, -0.4, 0.3, 0.6, -0.2, 0.4)
+
+# coupled_6dof_problem's constants, written out (no RNG): per joint the frame's
+# roll-pitch-yaw, its origin, the (unnormalised) axis, the link's mass and COM, and the
+# roll-pitch-yaw of the link's principal axes with the moments diag(0.5, 0.35, 0.2)·scale.
+COUPLED6_RPY = ((0.3, 0.0, 0.0), (0.0, -0.25, 0.4), (0.2, 0.15, -0.3), (-0.35, 0.1, 0.0),
+                (0.0, 0.3, 0.2), (0.25, -0.2, 0.1))
+COUPLED6_P = ((0.4, 0.1, 0.15), (0.8, -0.12, 0.08), (0.7, 0.15, -0.1), (0.6, -0.08, 0.2),
+              (0.5, 0.2, 0.05), (0.45, -0.05, -0.12))
+COUPLED6_AXIS = ((0.2, -0.3, 0.9), (0.25, 0.9, -0.3), (0.9, 0.2, 0.35), (-0.3, 0.25, 0.9),
+                 (0.2, -0.9, 0.3), (0.9, -0.35, 0.2))
+COUPLED6_MASS = (4.0, 3.4, 2.8, 2.2, 1.6, 1.0)
+COUPLED6_COM = ((0.30, 0.05, -0.10), (0.25, -0.08, 0.06), (0.20, 0.10, 0.04), (0.15, -0.05, -0.07),
+                (0.10, 0.04, 0.06), (0.08, -0.03, 0.05))
+COUPLED6_INERTIA_RPY = ((0.4, -0.3, 0.5), (-0.5, 0.2, 0.3), (0.3, 0.4, -0.6), (0.6, -0.2, -0.4),
+                        (-0.3, -0.5, 0.2), (0.2, 0.6, 0.4))
+COUPLED6_MOMENTS = (0.5, 0.35, 0.2)
+COUPLED6_INERTIA_SCALE = (1.0, 0.85, 0.7, 0.55, 0.4, 0.25)
+
+
+def coupled_6dof_problem(gravity: bool = True) -> ChainProblem:
+    """A six-joint chain without the 6Dof_arm's symmetries, for parity tests (not a
+    reference robot): every joint frame rotated (R0 ≠ R0ᵀ), joint origins with x, y and
+    z, oblique axes whose dominant component runs over z, y, x along the chain, distinct
+    masses, COMs off the origins in all three components, link inertias with three
+    distinct principal moments and all products of inertia nonzero; the 6-DoF arm's
+    costs and target. Every term of the recursion and of the task kinematics that
+    vanishes on the shipped arm (the COM cross products, ω × Iω, the parallel-axis
+    shift, R0·[a]× against [a]×·R0, p's y and z) is nonzero here:
+    tests/test_chain_oracle.py test_coupled_six_is_not_degenerate holds it to that."""
+    from .urdf import rpy_matrix
+    R0 = np.array([rpy_matrix(r) for r in COUPLED6_RPY])
+    axis = np.array([np.array(a) / math.sqrt(sum(v * v for v in a)) for a in COUPLED6_AXIS])
+    Ic = []
+    for r, k in zip(COUPLED6_INERTIA_RPY, COUPLED6_INERTIA_SCALE):
+        Rp = rpy_matrix(r)
+        I = Rp @ np.diag([k * v for v in COUPLED6_MOMENTS]) @ Rp.T
+        Ic.append(0.5 * (I + I.T))
+    g = np.array([0.0, 0.0, -9.81]) if gravity else np.zeros(3)
+    chain = Chain([f"joint_{i + 1}" for i in range(6)], R0, np.array(COUPLED6_P), axis,
+                  np.array(COUPLED6_MASS), np.array(COUPLED6_COM), np.array(Ic), g)
+    return ChainProblem(chain, 6, RBD_DT, RBD_TARGET_JOINTS_6DOF, RBD_Q_JOINT, RBD_R_JOINT, RBD_QF_JOINT)
 
 
 def rbd_6dof_problem(gravity: bool = False) -> ChainProblem:

@@ -1,22 +1,28 @@
-"""Fixtures of the six-joint chain (tests/test_gpu_chain6.py, tests/test_chain6_abi.py):
+"""Fixtures of the six-joint chain (tests/test_gpu_chain6.py, tests/test_chain6_abi.py,
+tests/test_gpu_chain6_general.py):
 
   chain6_t30.npz    rbd_6dof_problem(), gravity zero as the URDF parses, 3 trajectories
   chain6g_t30.npz   rbd_6dof_problem(gravity=True), 2 trajectories
   chain6g_cases_t30.npz   a line-search case (ls_*) and an x_traj case (xt_*) on the gravity
                     fixture's trajectories and gains (kept apart: each file stays under 160 KB)
+  chain6c_t24.npz   coupled_6dof_problem() (the general mechanism: no symmetry of the arm's
+                    left), 2 trajectories, T = 24
+  chain6c_cases_t24.npz   its line-search and x_traj cases
 
-Both through make_golden.chain_case (the numpy oracle: RNEA + RK4, exact Jacobians by
+All three targets (chain6, chain6g, chain6c) through make_golden.chain_case (the numpy
+oracle: RNEA + RK4, exact Jacobians by
 forward-mode AD, the generic oracle passes). The assertions below are conditions on the
 cases, so a regenerated fixture cannot hide a fragile one:
   * every Σδu² of every fit history is a factor ≥ 1.25 away from tol,
   * every fit line search takes one trial,
-  * the line-search case takes [4, 2] trials and every accept / reject margin exceeds
-    1 % of prev_cost.
+  * the line-search cases take [4, 2] (chain6g) and LS_TRIALS_C (chain6c) trials and every
+    accept / reject margin exceeds 1 % of prev_cost.
 Prints the oracle's literal-vs-symmetrised spread of the gains (the gain tolerance of the
 GPU tests may not be looser than 100× it).
 
-    python tests/golden/make_golden_chain6.py            # both (several minutes of CPU)
-    python tests/golden/make_golden_chain6.py chain6g    # one
+    python tests/golden/make_golden_chain6.py                 # all five files (several minutes of CPU)
+    python tests/golden/make_golden_chain6.py chain6g         # one target: chain6, chain6g or chain6c
+    python tests/golden/make_golden_chain6.py chain6c_cases   # chain6c_cases_t24 alone, from chain6c_t24
 """
 from __future__ import annotations
 
@@ -29,13 +35,17 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
 import make_golden as MG  # noqa: E402  (puts the repository and the package on sys.path)
-from ilqr_amd.chain import rbd_6dof_problem, rbd_initial_states  # noqa: E402
+from ilqr_amd.chain import coupled_6dof_problem, rbd_6dof_problem, rbd_initial_states  # noqa: E402
 from oracle import ilqr_oracle as O  # noqa: E402
 from oracle import rbd as RBD  # noqa: E402
 
 T, FIT_ITERS, TOL = 30, 20, 1e-6
 LS_SCALE = [9.0, 2.5]
 LS_TRIALS = [4, 2]
+# the general mechanism (ilqr_amd.chain.coupled_6dof_problem)
+T_C, SEED_C = 24, 81
+LS_SCALE_C = [9.0, 2.5]
+LS_TRIALS_C = [4, 2]
 
 
 class Recorder:
@@ -92,9 +102,10 @@ def closures(pr):
     return RBD.chain_closures(model, cost)
 
 
-def extend_gravity(name, cases, pr):
-    """The line-search and x_traj cases on the gravity fixture's trajectories and gains, in
-    a file of their own (`cases`): with them the fixture itself would pass the size limit."""
+def extend_gravity(name, cases, pr, ls_scale=LS_SCALE, want_trials=LS_TRIALS):
+    """The line-search and x_traj cases on the trajectories and gains of fixture `name` (the
+    gravity fixture, or the general mechanism's with its own ls_scale / want_trials), in a
+    file of their own (`cases`): with them the fixture itself would pass the size limit."""
     g = dict(np.load(os.path.join(HERE, name + ".npz")))
     f, l, lf = closures(pr)
     x, u, d, K = g["x"], g["u"], g["d"], g["K"]
@@ -106,22 +117,22 @@ def extend_gravity(name, cases, pr):
     ls_trials = np.empty(nb, dtype=np.int32)
     for b in range(nb):
         st = {}
-        ls_x[b], ls_u[b], ls_cost[b] = O.forward_pass(x[b], u[b], z, LS_SCALE[b] * d[b], K[b], ls_prev[b],
+        ls_x[b], ls_u[b], ls_cost[b] = O.forward_pass(x[b], u[b], z, ls_scale[b] * d[b], K[b], ls_prev[b],
                                                       f, l, lf, max_trials=MG.MAX_TRIALS, stats=st)
         ls_trials[b] = st["trials"]
         for j in range(1, st["trials"] + 1):  # every candidate's margin to prev_cost
-            _, _, cj = O.forward_pass(x[b], u[b], z, LS_SCALE[b] * d[b], K[b], np.inf, f, l, lf,
+            _, _, cj = O.forward_pass(x[b], u[b], z, ls_scale[b] * d[b], K[b], np.inf, f, l, lf,
                                       max_trials=1, alpha0=0.5 ** (j - 1))
             margin = (cj - ls_prev[b]) / ls_prev[b]
             print(f"{name}: ls trajectory {b} trial {j}: cost {cj:.6e} prev {ls_prev[b]:.6e} margin {margin:+.3f}")
             assert (margin < -0.01) if j == st["trials"] else (margin > 0.01), (b, j, margin)
-    assert ls_trials.tolist() == LS_TRIALS, ls_trials
+    assert ls_trials.tolist() == want_trials, ls_trials
     xt = 0.1 * x[:, ::-1]
     xt_x, xt_u, xt_cost = np.empty_like(x), np.empty_like(u), np.empty(nb)
     for b in range(nb):
         xt_x[b], xt_u[b], xt_cost[b] = O.forward_pass(x[b], u[b], xt[b], d[b], K[b], np.inf, f, l, lf,
                                                       max_trials=MG.MAX_TRIALS)
-    np.savez_compressed(os.path.join(HERE, cases + ".npz"), ls_scale=np.array(LS_SCALE), ls_prev_cost=ls_prev,
+    np.savez_compressed(os.path.join(HERE, cases + ".npz"), ls_scale=np.array(ls_scale), ls_prev_cost=ls_prev,
                         ls_trials=ls_trials, ls_x=ls_x, ls_u=ls_u, ls_cost=ls_cost, xt=xt, xt_x=xt_x,
                         xt_u=xt_u, xt_cost=xt_cost)
     print(name, "ls trials", ls_trials.tolist(), "A[6:, :6] max", np.abs(g["A"][..., 6:, :6]).max(),
@@ -145,7 +156,15 @@ def main(only=()):
                           tol=TOL, pr=pr, robot="6dof_arm+gravity")
         check_fits("chain6g_t30", rec)
         extend_gravity("chain6g_t30", "chain6g_cases_t30", pr)
-    for n in ("chain6_t30", "chain6g_t30", "chain6g_cases_t30"):
+    if want("chain6c"):
+        pr = coupled_6dof_problem()
+        with Recorder() as rec:
+            MG.chain_case("chain6c_t24", 6, rbd_initial_states(2, 6, seed0=SEED_C), T=T_C, fit_iters=FIT_ITERS,
+                          tol=TOL, pr=pr, robot="coupled_6dof")
+        check_fits("chain6c_t24", rec)
+    if want("chain6c") or want("chain6c_cases"):
+        extend_gravity("chain6c_t24", "chain6c_cases_t24", coupled_6dof_problem(), LS_SCALE_C, LS_TRIALS_C)
+    for n in ("chain6_t30", "chain6g_t30", "chain6g_cases_t30", "chain6c_t24", "chain6c_cases_t24"):
         p = os.path.join(HERE, n + ".npz")
         if os.path.exists(p):
             assert os.path.getsize(p) < 160 * 1024, (n, os.path.getsize(p))

@@ -231,3 +231,189 @@ def test_coupled_chain_is_not_degenerate():
     assert np.abs(m.bias_np(np.array([0.4, 0.9]), np.zeros(2))).max() > 1.0      # gravity
     g = np.load(os.path.join(os.path.dirname(__file__), "golden", "chain2c_t40.npz"))
     assert np.abs(g["A"][..., 2:, :2]).max() > 1e-3                                # ∂q̈/∂q
+
+
+# -- the general six-joint mechanism (ilqr_amd.chain.coupled_6dof_problem) -----------------
+@pytest.fixture(scope="module")
+def gen6():
+    from ilqr_amd.chain import coupled_6dof_problem
+    return coupled_6dof_problem()
+
+
+def test_coupled_six_is_not_degenerate(gen6):
+    """Every term that vanishes on the shipped 6-DoF arm is nonzero here, on the arrays
+    themselves and in what it does to one RK4 step: each of seven symmetrising edits of the
+    mechanism moves ChainModel.step by more than 1e-3 of its largest entry (on the shipped
+    arm transposing every R0 moves it by exactly 0)."""
+    import dataclasses
+    from ilqr_amd.chain import COUPLED6_RPY, RBD_TARGET_JOINTS_6DOF
+    ch = gen6.chain
+    assert ch.n == 6 and gen6.nu == 6 and tuple(gen6.target) == RBD_TARGET_JOINTS_6DOF
+    assert (gen6.q_weight == 100.0).all() and (gen6.r_weight == 10.0).all() and (gen6.qf_weight == 1e6).all()
+    assert np.array_equal(ch.gravity, [0.0, 0.0, -9.81])
+    assert len(set(COUPLED6_RPY)) == 6
+    assert all(sum(v != 0.0 for v in r) >= 2 for r in COUPLED6_RPY[1:]) and any(COUPLED6_RPY[0])
+    dominant = []
+    for i in range(6):
+        assert np.array_equal(ch.R0[i], rpy_matrix(COUPLED6_RPY[i]))
+        assert np.abs(ch.R0[i] - ch.R0[i].T).max() > 0.1                    # R0ᵀ ≠ R0
+        assert np.abs(ch.R0[i] @ ch.R0[i].T - np.eye(3)).max() < 1e-15
+        assert np.abs(ch.p[i]).min() >= 0.05 and np.abs(ch.com[i]).min() >= 0.03
+        assert np.abs(ch.axis[i]).min() > 0.15 and abs(np.linalg.norm(ch.axis[i]) - 1.0) < 1e-15
+        dominant.append(int(np.abs(ch.axis[i]).argmax()))
+        assert np.array_equal(ch.Ic[i], ch.Ic[i].T)
+        w = np.linalg.eigvalsh(ch.Ic[i])
+        assert w[0] > 0 and np.diff(w).min() > 0.1 * w[0]                    # SPD, distinct moments
+        assert w[0] + w[1] > w[2]                                            # a physical body's
+        assert min(abs(ch.Ic[i][0, 1]), abs(ch.Ic[i][0, 2]), abs(ch.Ic[i][1, 2])) > 1e-3
+    assert set(dominant) == {0, 1, 2} and all(a != b for a, b in zip(dominant, dominant[1:]))
+    assert len(set(ch.mass.tolist())) == 6
+
+    rng = np.random.default_rng(7)
+    X = np.concatenate([rng.uniform(-2, 2, (24, 6)), rng.uniform(-1, 1, (24, 6))], axis=1)
+    U = rng.uniform(-5, 5, (24, 6))
+    base = RBD.ChainModel(ch, 0.01).step(X, U)
+    p0 = ch.p.copy()
+    p0[:, 1:] = 0.0
+    ax = ch.axis.copy()
+    ax[:, 0] = 0.0
+    ax /= np.linalg.norm(ax, axis=1)[:, None]
+    edits = {"COMs zeroed": dict(com=np.zeros((6, 3))),
+             "products of inertia dropped": dict(Ic=np.array([np.diag(np.diag(I)) for I in ch.Ic])),
+             "isotropic inertias": dict(Ic=np.array([np.eye(3) * np.trace(I) / 3.0 for I in ch.Ic])),
+             "R0 transposed": dict(R0=np.array([R.T for R in ch.R0])),
+             "p's y and z zeroed": dict(p=p0),
+             "p's y and z swapped": dict(p=ch.p[:, [0, 2, 1]].copy()),
+             "axes' x component removed": dict(axis=ax)}
+    for what, kw in edits.items():
+        moved = RBD.ChainModel(dataclasses.replace(ch, **kw), 0.01).step(X, U)
+        r = np.abs(moved - base).max() / np.abs(base).max()
+        print(f"{what}: one RK4 step moves by {r:.2e} (relative)")
+        assert r > 1e-3, (what, r)
+
+
+def test_coupled_six_mass_matrix_independent_formulation(gen6):
+    m = RBD.ChainModel(gen6.chain)
+    rng = np.random.default_rng(1)
+    for _ in range(5):
+        q = rng.uniform(-3, 3, 6)
+        M = m.mass_matrix_np(q)
+        Mj = RBD.mass_matrix_jacobian(gen6.chain, q)
+        assert np.abs(M - Mj).max() < 1e-12 * np.abs(Mj).max()
+        assert np.abs(M - M.T).max() < 1e-12 * np.abs(M).max()
+        assert np.linalg.eigvalsh(M).min() > 0
+
+
+def test_coupled_six_rnea_inverts_forward_dynamics(gen6):
+    m = RBD.ChainModel(gen6.chain)
+    rng = np.random.default_rng(2)
+    q, qd, tau = rng.uniform(-2, 2, 6), rng.uniform(-1, 1, 6), rng.uniform(-3, 3, 6)
+    qdd = np.linalg.solve(m.mass_matrix_np(q), tau - m.bias_np(q, qd))
+    back = m.rnea([np.array([v]) for v in q], [np.array([v]) for v in qd], [np.array([v]) for v in qdd])
+    assert np.abs(np.array([v[0] for v in back]) - tau).max() < 1e-12
+
+
+def test_coupled_six_energy_conservation():
+    from ilqr_amd.chain import coupled_6dof_problem
+    m = RBD.ChainModel(coupled_6dof_problem(gravity=False).chain)
+    rng = np.random.default_rng(3)
+    x = np.concatenate([rng.uniform(-1, 1, 6), rng.uniform(-1, 1, 6)])[None]
+    u = np.zeros((1, 6))
+    ke = lambda x: 0.5 * x[0, 6:] @ m.mass_matrix_np(x[0, :6]) @ x[0, 6:]
+    e0 = ke(x)
+    for _ in range(100):
+        x = m.step(x, u)
+    assert abs(ke(x) - e0) < 1e-8 * e0
+
+
+def test_coupled_six_point_kinematics(gen6):
+    """oracle.cost_functions.point_position (the recursion tip to root, what the task
+    fixtures differentiate) against rbd.world_frames (root to tip, o + R·point)."""
+    from oracle import cost_functions as OC
+    rng = np.random.default_rng(5)
+    worst = 0.0
+    for q in rng.uniform(-3, 3, (6, 6)):
+        fr = RBD.world_frames(gen6.chain, q)
+        for body, pt in ((5, [0.05, 0.02, 0.1]), (2, [0.3, -0.2, 0.15]), (0, [-0.1, 0.25, 0.2])):
+            o, _, R = fr[body]
+            got = np.array(OC.point_position(gen6.chain, body, pt, [float(v) for v in q]), float)
+            worst = max(worst, np.abs(got - (o + R @ np.array(pt))).max())
+    print(f"point kinematics: max abs difference {worst:.2e}")
+    assert worst < 1e-14
+
+
+def test_coupled_six_c_restatement(gen6):
+    """The C restatement on the general chain: one RK4 step at the tolerance of
+    test_c_chain_dynamics_matches_numpy_oracle, and one cold iteration (central differences
+    against exact Jacobians) at test_c_chain_iteration_matches_numpy_oracle's."""
+    from oracle import cref
+    from oracle import ilqr_oracle as O
+    pr = gen6
+    model = RBD.ChainModel(pr.chain, pr.dt)
+    rng = np.random.default_rng(3)
+    X = rng.uniform(-1.5, 1.5, (40, 12))
+    U = rng.uniform(-2.0, 2.0, (40, 6))
+    ref = model.step(X, U)
+    out = cref.chain_dynamics(pr, X, U)
+    assert np.abs(out - ref).max() <= 1e-12 * max(1.0, np.abs(ref).max())
+    cost = RBD.ChainCost(pr.target, pr.q_weight, pr.r_weight, pr.qf_weight)
+    f, l, lf = RBD.chain_closures(model, cost)
+    T = 8
+    u = np.zeros((1, T, 6))
+    x = np.zeros((1, T + 1, 12))
+    x[:, 0] = rbd_initial_states(1, 6, seed0=81)
+    for t in range(T):
+        x[:, t + 1] = model.step(x[:, t], u[:, t])
+    d, K, xn, un, c, tr = cref.chain_iterate(pr, x, u)
+    assert (tr == 1).all()
+    do, Ko = O.backward_pass(x[0], u[0], f, l, lf, symmetrize=True)
+    assert np.abs(K[0] - Ko).max() <= 1e-6 * np.abs(Ko).max()
+    assert np.abs(d[0] - do).max() <= 1e-6 * np.abs(do).max()
+    xo, uo, co = O.forward_pass(x[0], u[0], np.zeros_like(x[0]), d[0], K[0], np.inf, f, l, lf)
+    assert np.abs(xn[0] - xo).max() <= 1e-12 * np.abs(xo).max()
+    assert abs(c[0] - co) <= 1e-12 * abs(co)
+
+
+def test_coupled_six_fixtures_consistent(gen6):
+    """The frozen general-chain fixtures against the oracle and the generators' conditions
+    (make_golden_chain6.py chain6c, make_golden_chain6_task.py), read back from the files."""
+    import json
+    from oracle import cost_functions as OC
+    z = np.load(os.path.join(GOLD, "chain6c_t24.npz"), allow_pickle=False)
+    assert z["x"].shape == (2, 25, 12) and z["u"].shape == (2, 24, 6)
+    assert np.array_equal(z["x"][:, 0], rbd_initial_states(2, 6, seed0=81))
+    assert json.loads(str(z["meta"]))["robot"] == "coupled_6dof"
+    model = RBD.ChainModel(gen6.chain, gen6.dt)
+    A, B = model.linearize(z["x"][:, 5], z["u"][:, 5])
+    assert np.allclose(A, z["A"][:, 5], rtol=0, atol=1e-14) and np.allclose(B, z["B"][:, 5], rtol=0, atol=1e-14)
+    assert np.abs(z["A"][..., 6:, :6]).max() > 0.05
+    assert (z["fit_status"] == 1).all() and z["fit_iters"].tolist() == [7, 10]
+    c = np.load(os.path.join(GOLD, "chain6c_cases_t24.npz"), allow_pickle=False)
+    assert c["ls_trials"].tolist() == [4, 2] and c["ls_scale"].tolist() == [9.0, 2.5]
+    assert np.array_equal(c["xt"], 0.1 * z["x"][:, ::-1])
+    assert (c["ls_cost"] < 0.99 * c["ls_prev_cost"]).all()
+    for name, seed0, body, euclidean in (("chain6ctask_euc_t24", 83, 5, True), ("chain6ctask_ref_t24", 81, 2, False)):
+        path = os.path.join(GOLD, name + ".npz")
+        assert os.path.getsize(path) < 160 * 1024
+        z = np.load(path, allow_pickle=False)
+        meta = json.loads(str(z["meta"]))
+        s = meta["simple"]
+        assert meta["robot"] == "coupled_6dof" and meta["T"] == 24
+        assert (s["body"], s["euclidean"]) == (body, euclidean) and all(v != 0.0 for v in s["point"])
+        assert np.array_equal(z["x"][:, 0], rbd_initial_states(2, 6, seed0=seed0))
+        for b, n in enumerate(z["fit_iters"]):
+            du2, tr = z["cond_du2"][b], z["cond_trials"][b]
+            r = du2[:n] / meta["tol"]
+            assert ((r >= 1.25) | (r <= 1.0 / 1.25)).all(), (name, b, du2[:n])
+            assert (tr[:n] == 1).all() and (tr[n:] == 0).all()
+            assert du2[n - 1] <= meta["tol"] and (du2[:n - 1] > meta["tol"]).all()
+        assert (z["fit_status"] == 1).all()
+        assert float(z["cond_gain_spread"]) < 1e-13
+        a = (gen6.chain, s["body"], s["point"], s["final_target"], s["weight"])
+        l, lf = OC.simple_immediate_cost(*a), OC.simple_final_cost(*a, euclidean=s["euclidean"])
+        x, u = z["fw_x"][1], z["fw_u"][1]
+        cost = 0.0
+        for t in range(u.shape[0]):
+            cost += l(list(x[t]), list(u[t]))
+        cost += lf(list(x[-1]))
+        assert abs(cost - z["fw_cost"][1]) <= 1e-14 * abs(cost), (name, cost, z["fw_cost"][1])

@@ -352,6 +352,69 @@ def test_coupled_chain_nu1(gpu, gc1, dtype, lin):
     assert rel(xn, gc1["fw_x"]) < t["fw"] * 10 and rel(c, gc1["fw_cost"]) < t["fw"] * 10
 
 
+def test_oblique_chain_vs_oracle(gpu, dyn_mode):
+    """coupled_2dof_problem(oblique=True): joint 2's frame turned about z, its axis off the
+    principal directions, its origin off the x axis — R0·[a]× against [a]×·R0, the R0·a·aᵀ
+    term and p's y and z, which the coupled chain leaves zero. fp64, both evaluators:
+      * the closed form passed its creation check (closed_form_error < 1e-9, include/ilqr.h)
+        and "auto" selects it, or it did not and "auto" is the recursion and "closed_form"
+        is refused;
+      * dynamics and the dual linearisation at 37 × 5 ragged points vs the oracle, at the
+        coupled chain's tolerances (1e-12; A, B 1e-11, ∂q̈/∂q against its own size 1e-9);
+      * the forward rollout (δu = K = 0) through the 16-lane rnea_cv group against the
+        dynamics kernel stepped (test_coupled_chain_forward_rollout's 1e-11 / 1e-10)."""
+    from ilqr_amd.chain import coupled_2dof_problem
+    from oracle import rbd
+    F = torch.float64
+    pr = coupled_2dof_problem(2, oblique=True)
+    model = rbd.ChainModel(pr.chain, pr.dt)
+    nb, T = 37, 5
+    s = _ChainSolver(pr, T, nb, dtype=F, linearization="dual")
+    err = s.closed_form_error
+    print(f"oblique chain: closed_form_error {err:.3e}, auto = {s.dynamics_mode}")
+    if err < 1e-9:
+        assert s.dynamics_mode == "closed_form"
+    else:
+        assert s.dynamics_mode == "rnea"
+        assert s.lib.ilqr_chain_set_dynamics(s.h, _lib.CHAIN_DYN_CLOSED_FORM) == _lib.ERR_UNSUPPORTED
+        if dyn_mode == "closed_form":
+            return   # one evaluator only: the "rnea" case of this test runs it
+    s.set_dynamics(dyn_mode)
+    assert s.dynamics_mode == dyn_mode
+    rng = np.random.default_rng(23)
+    x = np.concatenate([rng.uniform(-2.5, 2.5, (nb, T + 1, 2)), rng.uniform(-2, 2, (nb, T + 1, 2))], axis=2)
+    u = rng.uniform(-20, 20, (nb, T, 2))
+    xf, uf = x[:, :T].reshape(-1, 4), u.reshape(-1, 2)
+    ref = model.step(xf, uf)
+    Ar, Br = model.linearize(xf, uf)
+    xn = s.dynamics(dev(xf, F), dev(uf, F))
+    e, ev = rel(xn, ref), rel(xn[:, 2:], ref[:, 2:])
+    A, B = s.linearize(dev(x, F), dev(u, F))
+    A, B = A.reshape(-1, 4, 4), B.reshape(-1, 4, 2)
+    ea, eb, eq = rel(A, Ar), rel(B, Br), rel(A[:, 2:, :2], Ar[:, 2:, :2])
+    print(f"oblique chain[{dyn_mode}] dynamics {e:.3e} velocity rows {ev:.3e} A {ea:.3e} B {eb:.3e} "
+          f"A[2:, :2] {eq:.3e}")
+    assert e < 1e-12 and ev < 1e-12, (e, ev)
+    t = TOL[(F, "dual")]
+    assert ea < t["AB"] and eb < t["AB"], (ea, eb)
+    assert eq < 1e-9, eq
+    # the rollout of gentle inputs from the first states, both ways
+    ur = dev(u * 0.1, F)
+    x0 = dev(x[:, 0], F)
+    step = s.rollout(x0, ur)
+    x_in = torch.zeros((nb, T + 1, 4), dtype=F, device="cuda")
+    x_in[:, 0] = x0
+    pc = torch.full((nb,), float("inf"), dtype=F, device="cuda")
+    xr, un, _, tr, st = s.forward(x_in, ur, torch.zeros_like(ur), torch.zeros((nb, T, 2, 4), dtype=F, device="cuda"), pc)
+    assert (st.cpu().numpy() == 0).all() and (tr.cpu().numpy() == 1).all() and torch.equal(un, ur)
+    er, erv = rel(xr, step), rel(xr[..., 2:], step[..., 2:])
+    eo = rel(step[:, 1], model.step(x[:, 0], u[:, 0] * 0.1))
+    print(f"oblique chain[{dyn_mode}] forward vs dynamics stepped {er:.3e} velocity rows {erv:.3e}; "
+          f"first step vs oracle {eo:.3e}")
+    assert er < 1e-11 and erv < 1e-10, (er, erv)
+    assert eo < 1e-12, eo
+
+
 # -- BASELINE config 5 as stated: nu = 1, fp32, central differences, T = 100 ---------------
 @pytest.fixture(scope="module")
 def g5():
