@@ -20,17 +20,18 @@
 //    wave on the 4-block f64 MFMA for 2-joint chains, lane per trajectory otherwise)
 //    and the RK4 rollout + α-halving line search (a 16-lane group per trajectory,
 //    component-parallel Newton-Euler for chains of ≤ 3 joints), in the handle's dtype
-//    (fp32 or fp64). Six joints (the 6-DoF arm, fp64): the linearisation and the costs
-//    written as tiles for the wide tiles recursion (ilqr_tiles.hip) and a 32-lane
-//    forward group per trajectory — "Six-joint chains" below.
+//    (fp32 or fp64). Four to seven joints, every joint driven (the 6-DoF arm, a
+//    7-DoF manipulator; fp64): the linearisation and the costs written as tiles for the
+//    tiles recursion (ilqr_tiles.hip) and a 32-lane forward group per trajectory —
+//    "Chains on the tiles path" below.
 //  * cost_functions.jl's simple_final_cost / simple_immediate_cost (src/cost_functions.jl:
 //    5-54) in place of the joint-space costs: on 2-joint chains the point's coordinates as
 //    a polynomial sampled at the call (ChainTask, ilqr_chain_set_simple_costs, closed-form
-//    dynamics only); on six joints the kinematics composed on the device at every
+//    dynamics only); on the tiles path the kinematics composed on the device at every
 //    evaluation, analytic derivatives as the terminal tiles and the task cost inside the
 //    32-lane forward group (ChainTaskK, ilqr_chain_set_task_costs,
 //    ilqr_chain_final_cost_quadratize; fp64). ilqr_chain_set_simple_costs keeps refusing
-//    six joints, and a six-joint fp32 handle answers dynamics only.
+//    more than two joints, and an fp32 handle of more than two joints answers dynamics only.
 // Layout as the other families (include/ilqr.h): x (B, T+1, nx), u/d (B, T, nu),
 // K (B, T, nu, nx), trajectory slowest, nx = 2·n_joints.
 #include <hip/hip_runtime.h>
@@ -576,15 +577,16 @@ __device__ __forceinline__ double swap_rows(double x) {
   return __builtin_bit_cast(double, q);
 }
 
-// chain_xdot over a 32-lane group (six joints: seven passes do not fit the four roles of
-// a 16-lane group): eight quads, lane 4·role + c as in rnea_cv — role 0 the bias, roles
-// 1..NJ the columns of M, the rest idle passes (q̇ = q̈ = g = 0). The group is two DPP rows.
+// chain_xdot over a 32-lane group (four to seven joints: NJ + 1 passes do not fit the four
+// roles of a 16-lane group, and eight joints' nine do not fit this one's eight): eight quads,
+// lane 4·role + c as in rnea_cv — role 0 the bias, roles 1..NJ the columns of M, the rest
+// idle passes (q̇ = q̈ = g = 0). The group is two DPP rows.
 //  * sin/cos: lane n of EACH row evaluates joint min(n, NJ − 1), and row_newbcast:i hands
 //    joint i's pair to the row — one polynomial pair per lane, no cross-row traffic;
 //  * b and M: the rows swap their τ once (swap_rows); after it both rows hold the even
-//    row's τ (roles 0..3: b and columns 0..2) and the odd row's (roles 4..6: columns 3..5)
-//    and row_newbcast picks lane 4·(role mod 4) of either.
-// Every lane then eliminates the same 6×6 system in the scalar pass's order.
+//    row's τ (roles 0..3: b and columns 0..2) and the odd row's (roles 4..NJ: columns
+//    3..NJ − 1) and row_newbcast picks lane 4·(role mod 4) of either.
+// Every lane then eliminates the same NJ×NJ system in the scalar pass's order.
 template <int NJ, int NU>
 __device__ __forceinline__ void chain_xdot_cv32(const ChainK<double, NJ>& P, const double (&x)[2 * NJ],
                                                 const double (&u)[NU], double (&xd)[2 * NJ]) {
@@ -611,7 +613,10 @@ __device__ __forceinline__ void chain_xdot_cv32(const ChainK<double, NJ>& P, con
   V so, co;
   if (__builtin_expect(fabs(ang) > 1e5, 0)) sincos(ang, &so, &co);
   else sincos_reduced(ang, so, co);
-  auto rowlane = [](V v, int n) {  // lane n of the row (n a constant after unrolling)
+  // lane n of the row (n a constant after unrolling). The callers ask for lanes 0..NJ − 1
+  // (a joint's sin/cos) and 0, 4, 8, 12 (component 0 of a role): with NJ ≤ 7 that is
+  // 0..6, 8 and 12, the cases below
+  auto rowlane = [](V v, int n) {
     switch (n) {
       case 0: return qperm<QP_ROWBC + 0>(v);
       case 1: return qperm<QP_ROWBC + 1>(v);
@@ -1777,16 +1782,18 @@ __global__ __launch_bounds__(64 * W) void chain_iter_forward_trig_kernel(ChainTr
 }
 
 // ---------------------------------------------------------------------------
-// Six-joint chains (the 6-DoF arm, nx = 12, nu = 6, fp64). The Riccati recursion is the
-// wide tiles kernel (launch_tiles_backward, ilqr_tiles.hip), so the linearisation and the
-// costs are written as the tiles it reads — A (B,T,12,12), B (B,T,12,6), lx, lu, lxx, luu,
-// lfx, lfxx — and the forward runs a 32-lane group per trajectory (chain_xdot_cv32).
+// Chains on the tiles path (NJ = NU = 4..7 joints, every joint driven: the 6-DoF arm, a
+// 7-DoF manipulator; nx = 2·NJ, fp64). The Riccati recursion is a tiles kernel
+// (launch_tiles_backward, ilqr_tiles.hip: the narrow one for 8 × 4, the wide one beyond), so
+// the linearisation and the costs are written as the tiles it reads — A (B,T,nx,nx),
+// B (B,T,nx,nu), lx, lu, lxx, luu, lfx, lfxx — and the forward runs a 32-lane group per
+// trajectory (chain_xdot_cv32).
 // ---------------------------------------------------------------------------
 // chain_linearize_kernel's lane map (one lane per (b, t, direction)) and arithmetic; lane
 // kd stores column kd of A_t (kd < NX) or column kd − NX of B_t
-constexpr int CHAIN6_FD_WAVES = 1, CHAIN6_DUAL_WAVES = 1;
+constexpr int CHAIN_TILES_FD_WAVES = 1, CHAIN_TILES_DUAL_WAVES = 1;
 template <int NJ, int NU, int LIN>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LIN == ILQR_LINEARIZE_CENTRAL_FD ? CHAIN6_FD_WAVES : CHAIN6_DUAL_WAVES))) void chain_linearize_tiles_kernel(ChainK<double, NJ> P, int B, int T,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LIN == ILQR_LINEARIZE_CENTRAL_FD ? CHAIN_TILES_FD_WAVES : CHAIN_TILES_DUAL_WAVES))) void chain_linearize_tiles_kernel(ChainK<double, NJ> P, int B, int T,
                                                                     const double* __restrict__ x,
                                                                     const double* __restrict__ u,
                                                                     const int32_t* __restrict__ status,
@@ -1994,7 +2001,7 @@ __device__ __forceinline__ double chain_task_stage(const double (&u)[NU]) {
 // root-frame axis and origin of joint i (one root-to-tip pass of the joint transforms),
 // ∂p/∂qᵢ = âᵢ × (p − oᵢ) and ∂²p/∂qᵢ∂qⱼ = âᵢ × ∂p/∂qⱼ for i ≤ j ≤ body, zero beyond `body`.
 template <int NJ>
-__device__ void chain_task_quad6(const ChainK<double, NJ>& P, const ChainTaskK& C, const double (&q)[NJ],
+__device__ void chain_task_quad_fk(const ChainK<double, NJ>& P, const ChainTaskK& C, const double (&q)[NJ],
                                  double& cost, double (&g)[NJ], double (&H)[NJ][NJ]) {
   double p[3];
   chain_point_fk<NJ>(P, C, q, p);
@@ -2082,7 +2089,7 @@ __global__ __launch_bounds__(64) void chain_task_quad_kernel(ChainK<double, NJ> 
       for (int j = i; j < NJ; ++j) H[i][j] = i == j ? 2.0 * P.qfw[i] : 0.0;
     }
   } else {
-    chain_task_quad6<NJ>(P, C, q, c, g, H);
+    chain_task_quad_fk<NJ>(P, C, q, c, g, H);
   }
   if (cost) cost[b] = c;
   if (grad) {
@@ -2102,16 +2109,25 @@ __global__ __launch_bounds__(64) void chain_task_quad_kernel(ChainK<double, NJ> 
   }
 }
 
-// Forward rollout + α-halving line search of a six-joint chain: chain_forward_lane's
+// Forward rollout + α-halving line search of a chain on the tiles path: chain_forward_lane's
 // arithmetic in its order, every lane of a 32-lane group carrying the same x̄, ū, cost and
 // Σδu² (the dynamics split over the group: chain_xdot_cv32).
-//  * Step inputs (K_t 6×12, x_t, x_traj_t's joint rows, u_t, δu_t: 102 doubles) are loaded
-//    one step ahead, lane l the words l, l + 32, … of the step's record, and handed to
-//    the group through LDS at the top of the step (as 72 + 30 registers per lane and
-//    step in flight they would not fit);
-//  * x̄_t and ū_t are stored by lanes 0..11 and 12..17 (one coalesced store each).
-constexpr int CH6_LANES = 32;
-constexpr int CH6_STAGE = 128;  // doubles per group: 4 words per lane
+//  * Step inputs (K_t NU×NX, x_t, x_traj_t's joint rows, u_t, δu_t: N_IN = NU·NX + NX + NJ +
+//    2·NU doubles — 52, 75, 102, 133 for 4..7 joints) are loaded one step ahead, lane l the
+//    words l, l + 32, … of the step's record, and handed to the group through LDS at the
+//    top of the step (as registers per lane and step in flight they would not fit);
+//  * the staging is sized per instantiation: ⌈N_IN / 32⌉ words per lane (2, 3, 4, 5) and a
+//    stage of 32 × that many doubles (64, 96, 128, 160) per group;
+//  * x̄_t and ū_t are stored by lanes 0..NX − 1 and NX..NX + NU − 1 (one coalesced store each).
+constexpr int CH32_LANES = 32;
+template <int NJ, int NU>
+struct ChainStage {
+  static constexpr int N_IN = NU * 2 * NJ + 2 * NJ + NJ + 2 * NU;  // a step's record
+  static constexpr int WORDS = (N_IN + CH32_LANES - 1) / CH32_LANES;  // per lane
+  static constexpr int SIZE = CH32_LANES * WORDS;                     // doubles per group
+};
+static_assert(ChainStage<6, 6>::WORDS == 4 && ChainStage<6, 6>::SIZE == 128, "six joints: four words per lane");
+static_assert(ChainStage<7, 7>::WORDS == 5 && ChainStage<7, 7>::SIZE == 160, "seven joints: five words per lane");
 // TASK: the costs of a task mode (ℓ = Σū², ℓ_f the task cost C of x̄_N, every lane of the
 // group evaluating it on its own copy of x̄_N by the same code: the same bits in all 32) in
 // place of the joint-space ones, chosen at compile time so that the joint-cost
@@ -2129,8 +2145,10 @@ __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P
   using V = double;
   constexpr int NX = 2 * NJ, NK = NU * NX;
   constexpr int O_X = NK, O_XT = O_X + NX, O_U = O_XT + NJ, O_D = O_U + NU, N_IN = O_D + NU;
-  static_assert(N_IN <= CH6_STAGE && NX + NU <= CH6_LANES, "a step's inputs in four words per lane");
-  const int l32 = threadIdx.x & (CH6_LANES - 1);
+  constexpr int NW = ChainStage<NJ, NU>::WORDS;
+  static_assert(N_IN == ChainStage<NJ, NU>::N_IN && N_IN <= ChainStage<NJ, NU>::SIZE && NX + NU <= CH32_LANES,
+                "a step's inputs in NW words per lane, x̄ and ū stored by one lane each");
+  const int l32 = threadIdx.x & (CH32_LANES - 1);
   const V* xb0 = x + (size_t)b * (T + 1) * NX;
   const V* ub0 = u + (size_t)b * T * NU;
   const V* xt0 = (xtraj ? xtraj : x) + (size_t)b * (T + 1) * NX;
@@ -2139,13 +2157,13 @@ __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P
   const V* K0 = Kg + (size_t)b * T * NK;
   V* xo = xnew + (size_t)b * (T + 1) * NX;
   V* uo = unew + (size_t)b * T * NU;
-  // this lane's four words of a step's record: source and stride per step (a word past the
+  // this lane's NW words of a step's record: source and stride per step (a word past the
   // record re-reads K's first word and lands in the stage's unused tail)
-  const V* src[4];
-  int str[4];
+  const V* src[NW];
+  int str[NW];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int e = l32 + CH6_LANES * k;
+  for (int k = 0; k < NW; ++k) {
+    const int e = l32 + CH32_LANES * k;
     src[k] = K0, str[k] = 0;
     if (e < O_X) { src[k] = K0 + e; str[k] = NK; }
     else if (e < O_XT) { src[k] = xb0 + (e - O_X); str[k] = NX; }
@@ -2162,18 +2180,18 @@ __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P
     for (int i = 0; i < NX; ++i) xb[i] = xb0[i];  // x̄₁ = x₁ (:65)
     V cost = V(0);
     du2 = V(0);
-    V in[4];
+    V in[NW];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) in[k] = src[k][0];
+    for (int k = 0; k < NW; ++k) in[k] = src[k][0];
     for (int t = 0; t < T; ++t) {
       wave_lds_fence();  // the previous step's reads are done
 #pragma unroll
-      for (int k = 0; k < 4; ++k) stage[l32 + CH6_LANES * k] = in[k];
+      for (int k = 0; k < NW; ++k) stage[l32 + CH32_LANES * k] = in[k];
       wave_lds_fence();
       {
         const size_t tn = t + 1 < T ? t + 1 : t;  // step t + 1's words, in flight during step t
 #pragma unroll
-        for (int k = 0; k < 4; ++k) in[k] = src[k][tn * str[k]];
+        for (int k = 0; k < NW; ++k) in[k] = src[k][tn * str[k]];
       }
       V dx[NX];
 #pragma unroll
@@ -2254,7 +2272,19 @@ __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P
   return out;
 }
 
-constexpr int CH6_WG = 64;  // two trajectories per workgroup (one wave)
+constexpr int CH32_WG = 64;  // two trajectories per workgroup (one wave)
+
+// Bytes of a kernel's argument block (each argument at its natural alignment). ChainK is
+// passed by value and grows with the joint count — 2,832 bytes at seven joints — beside
+// ChainTaskK, ChainIter and LSParams: every forward kernel holds its own block to HIP's
+// 4 KB limit, so the largest instantiation is checked where it is compiled.
+template <class... A>
+constexpr size_t kernarg_bytes() {
+  size_t n = 0;
+  ((n = (n + alignof(A) - 1) / alignof(A) * alignof(A) + sizeof(A)), ...);
+  return n;
+}
+constexpr size_t HIP_KERNARG_LIMIT = 4096;
 
 // The two forward kernels. TaskK is empty (the joint-space cost) or ChainTaskK (a task mode:
 // the TASK instantiation of the group, the task cost's constants one more kernel argument).
@@ -2263,23 +2293,28 @@ constexpr int CH6_WG = 64;  // two trajectories per workgroup (one wave)
 // the middle of the list is never deduced: every launch spells out <NJ, NU> or
 // <NJ, NU, ChainTaskK>.
 template <int NJ, int NU, class... TaskK>
-__global__ __launch_bounds__(CH6_WG) void chain_forward32_kernel(
+__global__ __launch_bounds__(CH32_WG) void chain_forward32_kernel(
     ChainK<double, NJ> P, TaskK... C, int B, int T, const double* __restrict__ x, const double* __restrict__ u,
     const double* __restrict__ xtraj, const double* __restrict__ d, const double* __restrict__ K,
     const double* __restrict__ prev_cost, double* __restrict__ xnew, double* __restrict__ unew,
     double* __restrict__ new_cost, int32_t* __restrict__ trials, int32_t* __restrict__ status, LSParams ls) {
   static_assert((std::is_same_v<TaskK, ChainTaskK> && ...) && sizeof...(TaskK) <= 1, "TaskK: none or ChainTaskK");
+  static_assert(kernarg_bytes<ChainK<double, NJ>, TaskK..., int, int, const double*, const double*, const double*,
+                              const double*, const double*, const double*, double*, double*, double*, int32_t*,
+                              int32_t*, LSParams>() <= HIP_KERNARG_LIMIT,
+                "the chain constants by value: the argument block within HIP's limit");
+  constexpr int STAGE = ChainStage<NJ, NU>::SIZE;
   __shared__ ChainK<double, NJ> Ps;
-  __shared__ double stage[(CH6_WG / CH6_LANES) * CH6_STAGE];
-  chain_consts_to_lds<CH6_WG>(Ps, P);
-  const int b = (blockIdx.x * CH6_WG + threadIdx.x) / CH6_LANES;
+  __shared__ double stage[(CH32_WG / CH32_LANES) * STAGE];
+  chain_consts_to_lds<CH32_WG>(Ps, P);
+  const int b = (blockIdx.x * CH32_WG + threadIdx.x) / CH32_LANES;
   if (b >= B) return;  // the whole lane group
-  const int l32 = threadIdx.x & (CH6_LANES - 1);
+  const int l32 = threadIdx.x & (CH32_LANES - 1);
   const double pc = prev_cost ? prev_cost[b] : (double)INFINITY;
   const ChainFwdOut<double> r = chain_forward_group32<NJ, NU, sizeof...(TaskK) == 1>(
-      Ps, stage + (threadIdx.x / CH6_LANES) * CH6_STAGE, b, T, x, u, xtraj, d, K, pc, xnew, unew, nullptr, ls, C...);
+      Ps, stage + (threadIdx.x / CH32_LANES) * STAGE, b, T, x, u, xtraj, d, K, pc, xnew, unew, nullptr, ls, C...);
   // every lane of the group: the 32 lanes stride the copy of an exhausted search's inputs
-  fwd_finish<2 * NJ, NU>(b, T, r.cost, r.trials, r.accepted, x, u, xnew, unew, l32, CH6_LANES, new_cost, trials,
+  fwd_finish<2 * NJ, NU>(b, T, r.cost, r.trials, r.accepted, x, u, xnew, unew, l32, CH32_LANES, new_cost, trials,
                          status);
 }
 
@@ -2287,17 +2322,21 @@ __global__ __launch_bounds__(CH6_WG) void chain_forward32_kernel(
 // iteration's backward pass (it runs every trajectory): a NaN gain of a running
 // trajectory ends it here, as chain_iter_backward4_kernel does
 template <int NJ, int NU, class... TaskK>
-__global__ __launch_bounds__(CH6_WG) void chain_iter_forward32_kernel(ChainK<double, NJ> P, TaskK... C, int B, int T,
+__global__ __launch_bounds__(CH32_WG) void chain_iter_forward32_kernel(ChainK<double, NJ> P, TaskK... C, int B, int T,
                                                                      ChainIter<double> a,
                                                                      const int32_t* __restrict__ bstatus,
                                                                      LSParams ls) {
   static_assert((std::is_same_v<TaskK, ChainTaskK> && ...) && sizeof...(TaskK) <= 1, "TaskK: none or ChainTaskK");
+  static_assert(kernarg_bytes<ChainK<double, NJ>, TaskK..., int, int, ChainIter<double>, const int32_t*,
+                              LSParams>() <= HIP_KERNARG_LIMIT,
+                "the chain constants by value: the argument block within HIP's limit");
+  constexpr int STAGE = ChainStage<NJ, NU>::SIZE;
   __shared__ ChainK<double, NJ> Ps;
-  __shared__ double stage[(CH6_WG / CH6_LANES) * CH6_STAGE];
-  chain_consts_to_lds<CH6_WG>(Ps, P);
-  const int b = (blockIdx.x * CH6_WG + threadIdx.x) / CH6_LANES;
+  __shared__ double stage[(CH32_WG / CH32_LANES) * STAGE];
+  chain_consts_to_lds<CH32_WG>(Ps, P);
+  const int b = (blockIdx.x * CH32_WG + threadIdx.x) / CH32_LANES;
   if (b >= B || a.status[b] != ILQR_TRAJ_OK) return;  // the whole lane group
-  const int l32 = threadIdx.x & (CH6_LANES - 1);
+  const int l32 = threadIdx.x & (CH32_LANES - 1);
   if (bstatus[b] != ILQR_TRAJ_OK) {  // reference: AssertionError at backward_pass.jl:353
     if (l32 == 0) {
       a.status[b] = ILQR_TRAJ_NAN;
@@ -2308,7 +2347,7 @@ __global__ __launch_bounds__(CH6_WG) void chain_iter_forward32_kernel(ChainK<dou
   double du2 = 0.0;
   const double pc = a.prev_cost ? a.prev_cost[b] : (double)INFINITY;
   const ChainFwdOut<double> r = chain_forward_group32<NJ, NU, sizeof...(TaskK) == 1>(
-      Ps, stage + (threadIdx.x / CH6_LANES) * CH6_STAGE, b, T, a.x, a.u, a.xtraj, a.d, a.K, pc, a.xnew, a.unew, &du2,
+      Ps, stage + (threadIdx.x / CH32_LANES) * STAGE, b, T, a.x, a.u, a.xtraj, a.d, a.K, pc, a.xnew, a.unew, &du2,
       ls, C...);
   if (l32 != 0) return;
   fwd_iter_finish(a, b, r.cost, r.accepted, r.trials, du2, ls.tol);
@@ -2332,8 +2371,8 @@ struct ilqr_chain_handle {
   void* K = nullptr;
   void* d = nullptr;
   void* J = nullptr;
-  // six-joint chains: the derivative tiles the wide tiles kernel reads (fp64) and its
-  // per-trajectory status
+  // chains on the tiles path (4..7 joints, fp64): the derivative and cost tiles the tiles
+  // kernel reads and its per-trajectory status
   double *tA = nullptr, *tB = nullptr, *lx = nullptr, *lu = nullptr, *lxx = nullptr, *luu = nullptr;
   double *lfx = nullptr, *lfxx = nullptr;
   int32_t* bstatus = nullptr;
@@ -2354,7 +2393,7 @@ struct ilqr_chain_handle {
   const ilqr::ChainTask* task() const { return cost_mode == ILQR_CHAIN_COST_JOINT ? nullptr : task_dev; }
   // the same factories on the tiles path (ilqr_chain_set_task_costs): the kinematics are
   // composed on the device, these are the kernel argument
-  ilqr::ChainTaskK task6{};
+  ilqr::ChainTaskK taskk{};
   bool task_mode() const { return cost_mode != ILQR_CHAIN_COST_JOINT; }
 };
 
@@ -2592,7 +2631,7 @@ size_t vsize(const ilqr_chain_handle* h) { return h->dtype == ILQR_F32 ? 4 : 8; 
 // Typed operations of one (V, NJ, NU) instantiation. The iteration's parts (linearize,
 // backward, forward, iteration) exist for two joints only: the recursion is
 // chain_backward4's, four 4 × 4 trajectories per wave. Another joint count answers
-// `dynamics` alone (six joints iterate through Chain6Ops).
+// `dynamics` alone (four to seven joints iterate through ChainTilesOps).
 template <class V, int NJ, int NU>
 struct ChainOps {
   static constexpr int NX = 2 * NJ;
@@ -2699,11 +2738,13 @@ struct ChainOps {
   }
 };
 
-// The six-joint chain (nj = nu = 6, fp64): ChainOps' interface on the tiles path — the
-// linearisation and the costs written as tiles, launch_tiles_backward(12, 6), the 32-lane
-// forward group.
-struct Chain6Ops {
-  static constexpr int NJ = 6, NU = 6, NX = 12;
+// Chains of NJ = 4..7 joints, every joint driven (nu = NJ, fp64): ChainOps' interface on the
+// tiles path — the linearisation and the costs written as tiles,
+// launch_tiles_backward(2·NJ, NJ), the 32-lane forward group.
+template <int NJ_>
+struct ChainTilesOps {
+  static constexpr int NJ = NJ_, NU = NJ_, NX = 2 * NJ_;
+  static_assert(NJ > 3 && NJ + 1 <= 8, "the 32-lane forward group: one role per Newton-Euler pass");
   using Value = double;
   using V = double;
   using Iter = ilqr::ChainIter<double>;
@@ -2738,7 +2779,7 @@ struct Chain6Ops {
       return hipGetLastError();
     });
   }
-  // ilqr_chain_linearize: the name its generic lambda calls on ChainOps and Chain6Ops alike
+  // ilqr_chain_linearize: the name its generic lambda calls on ChainOps and ChainTilesOps alike
   static hipError_t linearize_to(ilqr_chain_handle* h, const V* x, const V* u, V* A, V* Bm) {
     return linearize(h, x, u, nullptr, A, Bm);
   }
@@ -2757,7 +2798,7 @@ struct Chain6Ops {
   static hipError_t quadratize(ilqr_chain_handle* h, const V* x, size_t stride, int n, const int32_t* st, V* cost,
                                V* grad, V* hess) {
     ilqr::chain_task_quad_kernel<NJ><<<(n + 63) / 64, 64, 0, h->stream>>>(
-        chain_consts<V, NJ>(h->chain), h->task6, h->task_mode() ? 0 : 1, n, x, stride, st, cost, grad, hess);
+        chain_consts<V, NJ>(h->chain), h->taskk, h->task_mode() ? 0 : 1, n, x, stride, st, cost, grad, hess);
     return hipGetLastError();
   }
   static ilqr::TileParams tile_params(const ilqr_chain_handle* h) {
@@ -2774,12 +2815,12 @@ struct Chain6Ops {
                             const V* K, const V* pc, V* xn, V* un, V* nc, int32_t* tr, int32_t* st,
                             const ilqr::LSParams& ls) {
     const auto P = chain_consts<V, NJ>(h->chain);
-    const int grid = (h->batch * ilqr::CH6_LANES + ilqr::CH6_WG - 1) / ilqr::CH6_WG;
+    const int grid = (h->batch * ilqr::CH32_LANES + ilqr::CH32_WG - 1) / ilqr::CH32_WG;
     if (h->task_mode())
-      ilqr::chain_forward32_kernel<NJ, NU, ilqr::ChainTaskK><<<grid, ilqr::CH6_WG, 0, h->stream>>>(
-          P, h->task6, h->batch, h->T, x, u, xt, d, K, pc, xn, un, nc, tr, st, ls);
+      ilqr::chain_forward32_kernel<NJ, NU, ilqr::ChainTaskK><<<grid, ilqr::CH32_WG, 0, h->stream>>>(
+          P, h->taskk, h->batch, h->T, x, u, xt, d, K, pc, xn, un, nc, tr, st, ls);
     else
-      ilqr::chain_forward32_kernel<NJ, NU><<<grid, ilqr::CH6_WG, 0, h->stream>>>(P, h->batch, h->T, x, u, xt, d, K,
+      ilqr::chain_forward32_kernel<NJ, NU><<<grid, ilqr::CH32_WG, 0, h->stream>>>(P, h->batch, h->T, x, u, xt, d, K,
                                                                                pc, xn, un, nc, tr, st, ls);
     return hipGetLastError();
   }
@@ -2792,40 +2833,65 @@ struct Chain6Ops {
                                     h->stream);
     if (e != hipSuccess) return e;
     const auto P = chain_consts<V, NJ>(h->chain);
-    const int grid = (h->batch * ilqr::CH6_LANES + ilqr::CH6_WG - 1) / ilqr::CH6_WG;
+    const int grid = (h->batch * ilqr::CH32_LANES + ilqr::CH32_WG - 1) / ilqr::CH32_WG;
     if (h->task_mode())
-      ilqr::chain_iter_forward32_kernel<NJ, NU, ilqr::ChainTaskK><<<grid, ilqr::CH6_WG, 0, h->stream>>>(
-          P, h->task6, h->batch, h->T, a, h->bstatus, ls);
+      ilqr::chain_iter_forward32_kernel<NJ, NU, ilqr::ChainTaskK><<<grid, ilqr::CH32_WG, 0, h->stream>>>(
+          P, h->taskk, h->batch, h->T, a, h->bstatus, ls);
     else
-      ilqr::chain_iter_forward32_kernel<NJ, NU><<<grid, ilqr::CH6_WG, 0, h->stream>>>(P, h->batch, h->T, a,
+      ilqr::chain_iter_forward32_kernel<NJ, NU><<<grid, ilqr::CH32_WG, 0, h->stream>>>(P, h->batch, h->T, a,
                                                                                     h->bstatus, ls);
     return hipGetLastError();
   }
 };
 
 // (n_joints, nu) shapes with compiled kernels in every dtype: the iLQR iteration for the
-// 2-DoF arm (nu = 2 every joint driven, nu = 1 joint 1 only); dynamics also for the 6-DoF arm.
+// 2-DoF arm (nu = 2 every joint driven, nu = 1 joint 1 only); dynamics also for the shapes
+// of the tiles path: 4..7 joints, every joint driven (three joints have no 32-lane group,
+// eight joints' nine Newton-Euler passes do not fit its eight roles).
 bool iter_supported(int nj, int nu) { return nj == 2 && (nu == 1 || nu == 2); }
-bool dyn_supported(int nj, int nu) { return iter_supported(nj, nu) || (nj == 6 && nu == 6); }
-// ... and per dtype: the 6-DoF arm iterates in fp64 only (its recursion is the f64 MFMA
+bool tiles_shape(int nj, int nu) { return nj >= 4 && nj <= 7 && nu == nj; }
+bool dyn_supported(int nj, int nu) { return iter_supported(nj, nu) || tiles_shape(nj, nu); }
+// ... and per dtype: the tiles path iterates in fp64 only (its recursion is the f64 MFMA
 // tiles kernel)
 bool iter_supported_dtype(int nj, int nu, int32_t dtype) {
   if (dtype != ILQR_F32 && dtype != ILQR_F64) return false;
-  return iter_supported(nj, nu) || (nj == 6 && nu == 6 && dtype == ILQR_F64);
+  return iter_supported(nj, nu) || (tiles_shape(nj, nu) && dtype == ILQR_F64);
 }
 bool handle_iterates(const ilqr_chain_handle* h) { return iter_supported_dtype(h->nj, h->nu, h->dtype); }
+// the handle iterates on the tiles path: its workspace is the tiles, its cost modes
+// ilqr_chain_set_task_costs'
+bool on_tiles(const ilqr_chain_handle* h) { return tiles_shape(h->nj, h->nu) && handle_iterates(h); }
 
 // fn(the handle's typed operations). DYN: the call is ilqr_chain_dynamics, which every
 // dyn_supported shape answers from ChainOps in either dtype; otherwise the shapes and
 // dtypes that iterate.
+template <class V, bool DYN, int NJ, class Fn>
+hipError_t dispatch_tiles(Fn&& fn) {
+  if constexpr (DYN) return fn(ChainOps<V, NJ, NJ>{});
+  else if constexpr (std::is_same_v<V, double>) return fn(ChainTilesOps<NJ>{});
+  else return hipErrorInvalidValue;
+}
 template <class V, bool DYN = false, class Fn>
 hipError_t dispatch(const ilqr_chain_handle* h, Fn&& fn) {
   if (h->nj == 2 && h->nu == 2) return fn(ChainOps<V, 2, 2>{});
   if (h->nj == 2 && h->nu == 1) return fn(ChainOps<V, 2, 1>{});
-  if (h->nj == 6 && h->nu == 6) {
-    if constexpr (DYN) return fn(ChainOps<V, 6, 6>{});
-    else if constexpr (std::is_same_v<V, double>) return fn(Chain6Ops{});
-  }
+  if (tiles_shape(h->nj, h->nu)) switch (h->nj) {
+      case 4: return dispatch_tiles<V, DYN, 4>(fn);
+      case 5: return dispatch_tiles<V, DYN, 5>(fn);
+      case 6: return dispatch_tiles<V, DYN, 6>(fn);
+      case 7: return dispatch_tiles<V, DYN, 7>(fn);
+    }
+  return hipErrorInvalidValue;
+}
+// fn(ChainTilesOps<nj>{}) of a handle on the tiles path
+template <class Fn>
+hipError_t with_tiles_ops(const ilqr_chain_handle* h, Fn&& fn) {
+  if (on_tiles(h)) switch (h->nj) {
+      case 4: return fn(ChainTilesOps<4>{});
+      case 5: return fn(ChainTilesOps<5>{});
+      case 6: return fn(ChainTilesOps<6>{});
+      case 7: return fn(ChainTilesOps<7>{});
+    }
   return hipErrorInvalidValue;
 }
 template <bool DYN = false, class Fn>
@@ -2919,13 +2985,18 @@ void apply_cost_mode(ilqr_chain_handle* h, int32_t mode) {
   h->cost_mode = mode;
 }
 
-// A six-joint handle's cost mode: the weights the per-step tiles and the forward read and the
-// Hessian tiles that go with them, enqueued on the handle's stream as at creation (launches
-// take the weights by value, in stream order). h->task6 is set by the caller.
-ilqr_status chain6_set_cost_mode(ilqr_chain_handle* h, int32_t mode) {
+// lxx, luu, lfxx of a handle on the tiles path, for its cost in effect
+hipError_t tiles_hessians(ilqr_chain_handle* h) {
+  return with_tiles_ops(h, [&](auto ops) { return decltype(ops)::hessians(h); });
+}
+
+// The cost mode of a handle on the tiles path: the weights the per-step tiles and the forward
+// read and the Hessian tiles that go with them, enqueued on the handle's stream as at creation
+// (launches take the weights by value, in stream order). h->taskk is set by the caller.
+ilqr_status chain_tiles_set_cost_mode(ilqr_chain_handle* h, int32_t mode) {
   CH_TRY(hipSetDevice(h->device));
   apply_cost_mode(h, mode);
-  CH_TRY(Chain6Ops::hessians(h));
+  CH_TRY(tiles_hessians(h));
   return ILQR_OK;
 }
 
@@ -2966,7 +3037,7 @@ ilqr_status ilqr_chain_create(ilqr_chain_handle** out, int device, const ilqr_ch
   h->created = *chain;
   const size_t w = vsize(h), B = (size_t)batch, nx = 2 * (size_t)h->nj, nu = (size_t)h->nu;
   hipError_t e = hipSuccess;
-  const bool six = h->nj == 6;
+  const bool tiles = on_tiles(h);
   if (handle_iterates(h)) {  // dynamics-only shapes need no workspace
     for (int i = 0; i < 2 && e == hipSuccess; ++i) {
       e = hipMalloc(&h->xbuf[i], w * B * (T + 1) * nx);
@@ -2974,8 +3045,8 @@ ilqr_status ilqr_chain_create(ilqr_chain_handle** out, int device, const ilqr_ch
     }
     if (e == hipSuccess) e = hipMalloc(&h->K, w * B * T * nu * nx);
     if (e == hipSuccess) e = hipMalloc(&h->d, w * B * T * nu);
-    if (e == hipSuccess && !six) e = hipMalloc(&h->J, w * B * T * (nx * (nx + nu) + nx + nu));
-    if (six) {  // the tiles in place of the records
+    if (e == hipSuccess && !tiles) e = hipMalloc(&h->J, w * B * T * (nx * (nx + nu) + nx + nu));
+    if (tiles) {  // the tiles in place of the records
       auto tile = [&](double** p, size_t n) {
         if (e == hipSuccess) e = hipMalloc(p, sizeof(double) * n);
       };
@@ -3005,8 +3076,8 @@ ilqr_status ilqr_chain_create(ilqr_chain_handle** out, int device, const ilqr_ch
     ilqr_chain_destroy(h);
     return chain_hip_fail(e, "ilqr_chain_create: closed-form dynamics");
   }
-  if (six && handle_iterates(h)) {
-    e = Chain6Ops::hessians(h);
+  if (tiles) {
+    e = tiles_hessians(h);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) {
       ilqr_chain_destroy(h);
@@ -3023,7 +3094,7 @@ ilqr_status ilqr_chain_set_dynamics(ilqr_chain_handle* h, int32_t mode) {
     return ILQR_ERR_BAD_ARG;
   if (mode == ILQR_CHAIN_DYN_CLOSED_FORM && !h->trig_ok) return ILQR_ERR_UNSUPPORTED;
   // the task-space final cost is evaluated by the closed-form forward only
-  // (2-joint chains; six joints compose the kinematics beside the recursion)
+  // (2-joint chains; the tiles path composes the kinematics beside the recursion)
   if (mode == ILQR_CHAIN_DYN_RNEA && h->cost_mode != ILQR_CHAIN_COST_JOINT && iter_supported(h->nj, h->nu))
     return ILQR_ERR_UNSUPPORTED;
   h->dyn_mode = mode;
@@ -3038,7 +3109,7 @@ ilqr_status ilqr_chain_set_simple_costs(ilqr_chain_handle* h, int32_t mode, int3
   if (st != ILQR_OK) return st;
   if (mode == ILQR_CHAIN_COST_JOINT) {  // the joint-space costs the handle was created with
     if (h->cost_mode != ILQR_CHAIN_COST_JOINT) {
-      if (h->nj == 6) return chain6_set_cost_mode(h, ILQR_CHAIN_COST_JOINT);  // its tiles too
+      if (on_tiles(h)) return chain_tiles_set_cost_mode(h, ILQR_CHAIN_COST_JOINT);  // its tiles too
       CH_TRY(hipStreamSynchronize(h->stream));  // launches in flight still read the old cost
       apply_cost_mode(h, ILQR_CHAIN_COST_JOINT);
     }
@@ -3072,29 +3143,31 @@ ilqr_status ilqr_chain_set_task_costs(ilqr_chain_handle* h, int32_t mode, int32_
   const ilqr_status st = check_cost_args(h, mode, body, point, final_target, weight);
   if (st != ILQR_OK) return st;
   if (mode == ILQR_CHAIN_COST_JOINT)
-    return h->cost_mode == ILQR_CHAIN_COST_JOINT ? ILQR_OK : chain6_set_cost_mode(h, ILQR_CHAIN_COST_JOINT);
-  if (h->nj != 6 || !handle_iterates(h)) {
-    g_chain_error = "ilqr_chain_set_task_costs: needs a handle that iterates on the tiles path (six joints, fp64)";
+    return h->cost_mode == ILQR_CHAIN_COST_JOINT ? ILQR_OK : chain_tiles_set_cost_mode(h, ILQR_CHAIN_COST_JOINT);
+  if (!on_tiles(h)) {
+    g_chain_error = "ilqr_chain_set_task_costs: needs a handle that iterates on the tiles path (4 to 7 joints, fp64)";
     return ILQR_ERR_UNSUPPORTED;
   }
   for (int k = 0; k < 3; ++k) {
-    h->task6.pt[k] = point[k];
-    h->task6.t[k] = final_target[k];
+    h->taskk.pt[k] = point[k];
+    h->taskk.t[k] = final_target[k];
   }
-  h->task6.w = weight;
-  h->task6.body = body;
-  h->task6.literal = mode == ILQR_CHAIN_COST_SIMPLE ? 1 : 0;
-  return chain6_set_cost_mode(h, mode);
+  h->taskk.w = weight;
+  h->taskk.body = body;
+  h->taskk.literal = mode == ILQR_CHAIN_COST_SIMPLE ? 1 : 0;
+  return chain_tiles_set_cost_mode(h, mode);
 }
 
 ilqr_status ilqr_chain_final_cost_quadratize(ilqr_chain_handle* h, const void* x, int n, void* cost, void* grad,
                                              void* hess) {
   if (!h || !x) return ILQR_ERR_BAD_ARG;
   if (n <= 0) return ILQR_ERR_BAD_DIMS;
-  if (h->nj != 6 || !handle_iterates(h)) return ILQR_ERR_UNSUPPORTED;
+  if (!on_tiles(h)) return ILQR_ERR_UNSUPPORTED;
   CH_TRY(hipSetDevice(h->device));
-  CH_TRY(Chain6Ops::quadratize(h, (const double*)x, Chain6Ops::NX, n, nullptr, (double*)cost, (double*)grad,
-                               (double*)hess));
+  CH_TRY(with_tiles_ops(h, [&](auto ops) {
+    using O = decltype(ops);
+    return O::quadratize(h, (const double*)x, O::NX, n, nullptr, (double*)cost, (double*)grad, (double*)hess);
+  }));
   return ILQR_OK;
 }
 

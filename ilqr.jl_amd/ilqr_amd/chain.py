@@ -41,7 +41,8 @@ RBD_QF_JOINT = 10.0 * 100000.0          # jo_cost 10, euclidean_penalty * 100000
 
 def load_robot(name: str) -> Chain:
     """A chain description shipped with the package ('2dof_arm', '6dof_arm'; made from
-    the reference's test/urdf by tools/make_robots.py) or a path to a URDF file."""
+    the reference's test/urdf by tools/make_robots.py) or a path to a URDF file: a serial
+    chain of 4 to 7 revolute joints, every joint driven, iterates in fp64."""
     if name.endswith(".urdf"):
         return parse_urdf(name)
     with open(os.path.join(ROBOTS, name + ".json")) as f:
@@ -184,6 +185,50 @@ def coupled_6dof_problem(gravity: bool = True) -> ChainProblem:
     return ChainProblem(chain, 6, RBD_DT, RBD_TARGET_JOINTS_6DOF, RBD_Q_JOINT, RBD_R_JOINT, RBD_QF_JOINT)
 
 
+# coupled_chain_problem's seventh joint, written out like the six above (no RNG): a rotated
+# frame, an oblique axis, an origin with x, y and z, the COM off the origin, three distinct
+# principal moments turned off the link's axes (all products of inertia nonzero).
+COUPLED7_RPY = (-0.2, 0.25, -0.35)
+COUPLED7_P = (0.4, 0.12, 0.09)
+COUPLED7_AXIS = (-0.35, 0.3, 0.9)
+COUPLED7_MASS = 0.7
+COUPLED7_COM = (0.06, 0.04, -0.05)
+COUPLED7_INERTIA_RPY = (-0.4, 0.3, -0.5)
+COUPLED7_INERTIA_SCALE = 0.15
+# RBD_TARGET_JOINTS_6DOF and one more value
+RBD_TARGET_JOINTS_7DOF = RBD_TARGET_JOINTS_6DOF + (-0.3,)
+
+
+def coupled_chain_problem(n_joints: int, gravity: bool = True) -> ChainProblem:
+    """coupled_6dof_problem's mechanism with n_joints ∈ {4, 5, 6, 7} joints, every joint
+    driven (not a reference robot): the first n joints take its constants, a seventh has
+    constants of its own (COUPLED7_*), the targets are RBD_TARGET_JOINTS_7DOF[:n].
+    coupled_chain_problem(6) is coupled_6dof_problem() field by field. No symmetry of the
+    shipped arms is left at any count: tests/test_chainN_abi.py holds joint 7 to that."""
+    from .urdf import rpy_matrix
+    if n_joints not in (4, 5, 6, 7):
+        raise ValueError("coupled_chain_problem: n_joints must be 4, 5, 6 or 7")
+    n = n_joints
+    rpy = (COUPLED6_RPY + (COUPLED7_RPY,))[:n]
+    p = (COUPLED6_P + (COUPLED7_P,))[:n]
+    ax = (COUPLED6_AXIS + (COUPLED7_AXIS,))[:n]
+    mass = (COUPLED6_MASS + (COUPLED7_MASS,))[:n]
+    com = (COUPLED6_COM + (COUPLED7_COM,))[:n]
+    irpy = (COUPLED6_INERTIA_RPY + (COUPLED7_INERTIA_RPY,))[:n]
+    iscale = (COUPLED6_INERTIA_SCALE + (COUPLED7_INERTIA_SCALE,))[:n]
+    R0 = np.array([rpy_matrix(r) for r in rpy])
+    axis = np.array([np.array(a) / math.sqrt(sum(v * v for v in a)) for a in ax])
+    Ic = []
+    for r, k in zip(irpy, iscale):
+        Rp = rpy_matrix(r)
+        I = Rp @ np.diag([k * v for v in COUPLED6_MOMENTS]) @ Rp.T
+        Ic.append(0.5 * (I + I.T))
+    g = np.array([0.0, 0.0, -9.81]) if gravity else np.zeros(3)
+    chain = Chain([f"joint_{i + 1}" for i in range(n)], R0, np.array(p), axis, np.array(mass),
+                  np.array(com), np.array(Ic), g)
+    return ChainProblem(chain, n, RBD_DT, RBD_TARGET_JOINTS_7DOF[:n], RBD_Q_JOINT, RBD_R_JOINT, RBD_QF_JOINT)
+
+
 def rbd_6dof_problem(gravity: bool = False) -> ChainProblem:
     """The RBD example's joint-space costs on the shipped 6Dof_arm with a fixed base, every
     joint driven (fp64 iteration kernels). The URDF parses with zero gravity, as the
@@ -225,15 +270,15 @@ class ChainSolver:
                                               _lib.F32 if dtype == torch.float32 else _lib.F64,
                                               _LIN[linearization]), "ilqr_chain_create")
         self.h = h
-        # the iteration kernels of this shape in the solver's dtype (the 6-DoF arm: fp64 only)
+        # the iteration kernels of this shape in the solver's dtype (4 to 7 joints: fp64 only)
         self.iterates = bool(self.lib.ilqr_chain_supported_dtype(
             self.nj, self.nu, _lib.F32 if dtype == torch.float32 else _lib.F64))
 
     def set_dynamics(self, mode: str):
         """The iteration kernels' dynamics evaluator (2-joint chains): "auto" (the closed
         form when its creation check passed), "rnea" (the recursive Newton-Euler, the
-        restatement of RigidBodyDynamics.jl's calls) or "closed_form". Six joints run the
-        recursion: "auto" and "rnea" mean the same, "closed_form" is unsupported."""
+        restatement of RigidBodyDynamics.jl's calls) or "closed_form". Four to seven joints run
+        the recursion: "auto" and "rnea" mean the same, "closed_form" is unsupported."""
         m = {"auto": _lib.CHAIN_DYN_AUTO, "rnea": _lib.CHAIN_DYN_RNEA,
              "closed_form": _lib.CHAIN_DYN_CLOSED_FORM}[mode]
         _lib.check(self.lib.ilqr_chain_set_dynamics(self.h, m), "ilqr_chain_set_dynamics")
@@ -254,8 +299,8 @@ class ChainSolver:
         ℓ_f = weight·Σₖ (p_z − final_targetₖ)² for the point `point` of body `body`
         (0-based link index or the name of the joint that moves it; −1 = the base), or
         the squared distance Σₖ (pₖ − final_targetₖ)² with euclidean=True. A 2-joint
-        chain samples the point's closed form at this call; six joints (fp64) compose the
-        kinematics on the device at every evaluation (ilqr_chain_set_task_costs)."""
+        chain samples the point's closed form at this call; four to seven joints (fp64) compose
+        the kinematics on the device at every evaluation (ilqr_chain_set_task_costs)."""
         b = body_index(self.p.chain, body)
         pt = (C.c_double * 3)(*[float(v) for v in np.asarray(point, float).reshape(3)])
         tg = (C.c_double * 3)(*[float(v) for v in np.asarray(final_target, float).reshape(3)])
@@ -282,7 +327,7 @@ class ChainSolver:
     def final_cost_quadratization(self, x):
         """final_cost_quadratization (backward_pass.jl:134-153) of the cost in effect at the
         states x (n, nx): (ℓ_f (n,), ∇ℓ_f (n, nx), ∇²ℓ_f (n, nx, nx)) on the device
-        (ilqr_chain_final_cost_quadratize: six joints, fp64)."""
+        (ilqr_chain_final_cost_quadratize: four to seven joints, fp64)."""
         n = x.shape[0]
         _req(x, torch.float64, (n, self.nx), "x")
         cost = self._new(n, dtype=torch.float64)

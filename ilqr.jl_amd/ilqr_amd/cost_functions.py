@@ -20,7 +20,7 @@ robot name for load_robot); `body` is the index of the link joint `body` moves (
 joint's name; −1 = the fixed base). With ChainDynamics both callables are recognised by
 ilqr_amd.fit / backward_pass / forward_pass, which then solve on the device: a 2-joint
 chain with ilqr_chain_set_simple_costs (the task cost's coefficients are sampled once per
-handle), the 6-DoF arm (float64) with ilqr_chain_set_task_costs (the kinematics composed on
+handle), a chain of 4 to 7 joints (the 6-DoF arm; float64) with ilqr_chain_set_task_costs (the kinematics composed on
 the device at every evaluation); no host evaluation inside the iteration either way. Called
 directly they evaluate on the host (one state: the reference's closure semantics).
 """

@@ -886,7 +886,7 @@ function ChainSolver(c::Chain, nx::Integer, nu::Integer, T::Integer, nb::Integer
         if costs !== nothing
             mode = costs.euclidean ? ILQR_CHAIN_COST_SIMPLE_EUCLIDEAN : ILQR_CHAIN_COST_SIMPLE
             # by handle: the sampled closed form of the 2-joint family, or the kinematics composed
-            # on the device (six joints, fp64); the same argument list either way
+            # on the device (4 to 7 joints, fp64); the same argument list either way
             if ccall((:ilqr_chain_supported, libilqr), Cint, (Cint, Cint), c.n_joints, c.nu) == 1
                 check(ccall((:ilqr_chain_set_simple_costs, libilqr), Cint,
                             (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Float64),
@@ -927,9 +927,10 @@ the device precision, as the reference's generic Julia code would. `dynamics` pi
 2-joint evaluator (AUTO: the closed form sampled from the Newton-Euler recursion at
 creation; RNEA: the recursion itself). `costs = simple_costs(…)` replaces the chain's
 joint-space costs with cost_functions.jl's pair (2-joint chains: the closed form,
-ilqr_chain_set_simple_costs; six joints in fp64: ilqr_chain_set_task_costs). Nothing here
-depends on the joint count: the 6-DoF arm (n_joints = nu = 6) iterates in fp64
-(ilqr_chain_supported_dtype(6, 6, ILQR_F64) == 1), so it takes Array{Float64,3}; with
+ilqr_chain_set_simple_costs; 4 to 7 joints in fp64: ilqr_chain_set_task_costs). Nothing here
+depends on the joint count: a chain of n_joints = nu = 4, 5, 6 or 7 (the 6-DoF arm, a 7-DoF
+manipulator) iterates in fp64 (ilqr_chain_supported_dtype(n, n, ILQR_F64) == 1), so it takes
+Array{Float64,3}; with
 Array{Float32,3} ilqr_chain_fit returns ILQR_ERR_UNSUPPORTED. The handle
 and buffers are cached per (chain, T, batch, element type, options): an MPC loop calling
 chain_fit allocates nothing per call (clear_cache!() closes them)."""

@@ -129,7 +129,8 @@ const char* ilqr_status_string(ilqr_status s);
 const char* ilqr_last_error(void);
 void ilqr_default_options(ilqr_options* opts);
 /* 1 if (nx, nu) has a compiled kernel for `kind`. ILQR_PROBLEM_CHAIN answers through
- * ilqr_chain_supported (every dtype), so (12, 6) — the 6-DoF arm, fp64 only — is 0 here:
+ * ilqr_chain_supported (every dtype), so (12, 6) — the 6-DoF arm, fp64 only — and the other
+ * chains of more than two joints are 0 here:
  * ask ilqr_chain_supported_dtype. */
 int ilqr_supported(int32_t kind, int nx, int nu);
 
@@ -305,19 +306,25 @@ ilqr_status ilqr_fit_ex(ilqr_handle* h, const ilqr_problem* p, const ilqr_option
  * derivatives of dynamicsf are forward-mode duals (ForwardDiff's algorithm,
  * ILQR_LINEARIZE_DUAL) or central differences (ILQR_LINEARIZE_CENTRAL_FD).
  * Compiled shapes (ilqr_chain_supported_dtype): the 2-joint arm with nu = 1 or 2 in
- * either dtype, and the 6-DoF arm (n_joints = nu = 6) in ILQR_F64 — every entry point,
- * both linearisations, the argument, status, NaN and line-search semantics of the
- * 2-joint family. A six-joint ILQR_F32 handle answers ilqr_chain_dynamics only (the rest
- * returns ILQR_ERR_UNSUPPORTED); (6, 1) is not compiled. Six joints run the recursive
+ * either dtype, and serial chains of n_joints = nu = 4, 5, 6 or 7 (the 6-DoF arm, a 7-DoF
+ * manipulator; every joint driven) in ILQR_F64 — every entry point, both linearisations,
+ * the argument, status, NaN and line-search semantics of the 2-joint family. An ILQR_F32
+ * handle of 4 to 7 joints answers ilqr_chain_dynamics only (the rest returns
+ * ILQR_ERR_UNSUPPORTED). Not compiled (ilqr_chain_create returns ILQR_ERR_UNSUPPORTED):
+ * three joints and eight (the forward pass splits the NJ + 1 Newton-Euler passes of a step
+ * over the eight roles of a 32-lane group, which three joints do not need and nine passes
+ * do not fit), and (n, 1) for n > 2. Chains of 4 to 7 joints run the recursive
  * Newton-Euler only: ilqr_chain_set_simple_costs and ilqr_chain_set_dynamics(CLOSED_FORM)
- * return ILQR_ERR_UNSUPPORTED, AUTO and RNEA both mean the recursion. The task-space costs
- * of cost_functions.jl on six joints are ilqr_chain_set_task_costs (kinematics composed on
- * the device, fp64).
+ * return ILQR_ERR_UNSUPPORTED, AUTO and RNEA both mean the recursion. Their task-space
+ * costs of cost_functions.jl are ilqr_chain_set_task_costs (kinematics composed on the
+ * device, fp64).
  * Device memory taken at creation, per (trajectory, step): a 2-joint handle keeps one
- * linearisation record (nx(nx + nu) + nx + nu words), a six-joint fp64 handle the tiles
- * of the wide Riccati kernel instead — A 144, B 72, lxx 144, luu 36, lx 12, lu 6 doubles —
- * plus, for both, the gains (nu·nx + nu) and two trajectory buffers (2(nx + nu)):
- * 528 doubles = 4224 bytes per (trajectory, step) for six joints.
+ * linearisation record (nx(nx + nu) + nx + nu words), an fp64 handle of 4 to 7 joints the
+ * tiles of the Riccati tiles kernel instead — A nx², B nx·nu, lxx nx², luu nu², lx nx, lu nu
+ * doubles — plus, for both, the gains (nu·nx + nu) and two trajectory buffers (2(nx + nu)):
+ * 2nx² + 2nx·nu + nu² + 3nx + 4nu doubles on the tiles path, which with nx = 2n, nu = n is
+ * 13n² + 10n — 248, 375, 528 and 707 doubles (1984, 3000, 4224 and 5656 bytes) per
+ * (trajectory, step) for 4, 5, 6 and 7 joints.
  * --------------------------------------------------------------------------- */
 #define ILQR_CHAIN_MAX_JOINTS 8
 
@@ -344,11 +351,13 @@ typedef struct {
 typedef struct ilqr_chain_handle ilqr_chain_handle;
 
 /* 1 if the iteration kernels are compiled for this shape in EVERY dtype: (2, 1) and
- * (2, 2). 0 for the 6-DoF arm, which iterates in fp64 only. */
+ * (2, 2). 0 for chains of 4 to 7 joints (the 6-DoF arm among them), which iterate in fp64
+ * only. */
 int ilqr_chain_supported(int n_joints, int nu);
 /* 1 if the iteration kernels (linearize, backward, forward, iterate, fit) are compiled
- * for this shape in `dtype`: (2, 1 or 2) in ILQR_F32 and ILQR_F64, (6, 6) in ILQR_F64.
- * 0 otherwise, an invalid dtype included. */
+ * for this shape in `dtype`: (2, 1 or 2) in ILQR_F32 and ILQR_F64; (4, 4), (5, 5), (6, 6)
+ * and (7, 7) in ILQR_F64. 0 otherwise — (3, 3), (8, 8), (n, 1) for n > 2, a partially driven
+ * chain, an invalid dtype. */
 int ilqr_chain_supported_dtype(int n_joints, int nu, int32_t dtype);
 const char* ilqr_chain_last_error(void);
 ilqr_status ilqr_chain_create(ilqr_chain_handle** out, int device, const ilqr_chain* chain, int T,
@@ -398,23 +407,23 @@ ilqr_status ilqr_chain_set_simple_costs(ilqr_chain_handle* h, int32_t mode, int3
                                         double weight);
 /* cost_functions.jl's factories with the point's kinematics composed on the device at
  * every evaluation (no sampled closed form): any handle that iterates on the tiles path
- * (six joints, fp64). mode / body / point / final_target / weight as
+ * (4 to 7 joints, fp64). mode / body / point / final_target / weight as
  * ilqr_chain_set_simple_costs; ILQR_CHAIN_COST_JOINT restores the handle's joint costs.
  * The Hessian tiles of the new mode are enqueued on the handle's stream. On a 2-joint
  * handle the call forwards to ilqr_chain_set_simple_costs (its returns, its closed-form
- * requirement), so one name serves every handle; a handle that does not iterate (six
+ * requirement), so one name serves every handle; a handle that does not iterate (4 to 7
  * joints, ILQR_F32) returns ILQR_ERR_UNSUPPORTED; a body outside −1..n_joints−1, a NULL or
  * non-finite point / final_target / weight return ILQR_ERR_BAD_ARG and leave the mode as
- * it was. ilqr_chain_set_dynamics(RNEA / AUTO) stays accepted on six joints while a task
- * cost is set. ilqr_chain_set_simple_costs itself keeps refusing a task mode on six
- * joints (it is the sampled closed form). */
+ * it was. ilqr_chain_set_dynamics(RNEA / AUTO) stays accepted on the tiles path while a
+ * task cost is set. ilqr_chain_set_simple_costs itself keeps refusing a task mode on more
+ * than two joints (it is the sampled closed form). */
 ilqr_status ilqr_chain_set_task_costs(ilqr_chain_handle* h, int32_t mode, int32_t body,
                                       const double* point, const double* final_target,
                                       double weight);
 /* final_cost_quadratization (backward_pass.jl:134-153) of the handle's cost in effect at
  * n states: cost (n), grad (n, nx), hess (n, nx, nx); any of the three may be NULL.
- * x (n, nx), fp64, device memory; enqueued on the handle's stream. Six-joint ILQR_F64
- * handles (ILQR_ERR_UNSUPPORTED elsewhere). hess is exactly symmetric and its velocity
+ * x (n, nx), fp64, device memory; enqueued on the handle's stream. ILQR_F64 handles of
+ * 4 to 7 joints (ILQR_ERR_UNSUPPORTED elsewhere). hess is exactly symmetric and its velocity
  * rows and columns are exactly 0. */
 ilqr_status ilqr_chain_final_cost_quadratize(ilqr_chain_handle* h, const void* x, int n,
                                              void* cost, void* grad, void* hess);

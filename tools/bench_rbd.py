@@ -1,5 +1,6 @@
 """Secondary benchmark (--robot 6dof_arm: the same step on the shipped 6-DoF arm, nx = 12,
-nu = 6, fp64): BASELINE config 5 — the RBD example (RigidBodyDynamics-style
+nu = 6, fp64; --robot coupled --joints N: on ilqr_amd.chain.coupled_chain_problem(N), N = 4, 5,
+6 or 7 joints, nx = 2N, nu = N, fp64): BASELINE config 5 — the RBD example (RigidBodyDynamics-style
 dynamics of test/urdf/2Dof_arm.urdf, fixed base: nx = 4, nu = 1 as the config states, or
 --nu 2), T = 100,
 batch 2048 random x₀, fp32, linearised on the device by central finite differences
@@ -24,7 +25,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "ilqr.jl_amd")]
 
 from ilqr_amd import _lib  # noqa: E402
-from ilqr_amd.chain import ChainSolver, rbd_2dof_problem, rbd_6dof_problem, rbd_initial_states  # noqa: E402
+from ilqr_amd.chain import (ChainSolver, coupled_chain_problem, rbd_2dof_problem, rbd_6dof_problem,  # noqa: E402
+                            rbd_initial_states)
 from tools import flops as FL  # noqa: E402
 
 # --simple-cost: the task cost of tests/golden/chain6task_euc_t30 (six joints)
@@ -66,7 +68,8 @@ def cpu_baseline(pr, x, u, budget_s):
 
 
 def measure(lin="fd", B=2048, T=100, nu=1, dtype="f32", steps=100, warmup=100, device=0,
-            dynamics="auto", cpu_budget=None, base=None, problem=None, simple_cost=False):
+            dynamics="auto", cpu_budget=None, base=None, problem=None, simple_cost=False, robot=None,
+            fit=True):
     """Config 5's fit-iteration rate and per-kernel roofline for one linearisation (one
     dict; bench.py's secondary_configs calls this after its headline, outside the
     headline's timed region)."""
@@ -130,7 +133,8 @@ def measure(lin="fd", B=2048, T=100, nu=1, dtype="f32", steps=100, warmup=100, d
     fw_fl = FL.forward_flops_per_step(pr.nx, pr.nu, f_rk4) * T * B
     peak = PEAK_TFLOPS[dtype]
     # lanes per trajectory of the forward that runs: 4 line-search candidates on the closed
-    # form, a 16-lane Newton-Euler group on the 2-joint recursion, 32 lanes for six joints
+    # form, a 16-lane Newton-Euler group on the 2-joint recursion, 32 lanes on the tiles path
+    # (4 to 7 joints)
     fw_lanes = 4 if s.dynamics_mode == "closed_form" else (16 if pr.n_joints <= 3 else 32)
     kern = {"linearize": (lin_ms, lin_fl), "riccati": (max(bw_ms - lin_ms, 1e-6), ric_fl),
             "forward": (fw_ms, fw_fl)}
@@ -152,14 +156,15 @@ def measure(lin="fd", B=2048, T=100, nu=1, dtype="f32", steps=100, warmup=100, d
     # latency of one step — the FLOP fraction is small by construction
     roof["forward"]["step_latency_ns"] = fw_ms * 1e6 / T
     roof["forward"]["lanes_busy_frac"] = min(1.0, (4 if pr.n_joints == 2 else fw_lanes) * B / (1024 * 64))
-    six = pr.n_joints != 2
+    tiles = pr.n_joints > 2   # the tiles path: 4 to 7 joints, fp64
+    what = robot or f"the shipped {pr.n_joints}-DoF arm"
     res = {"metric": f"batched iLQR iterations/sec (fwd+bwd pass), RBD {pr.n_joints}-DoF arm fixed base, "
                      f"nx={pr.nx} nu={pr.nu} T={T}",
            "value": 1000.0 / ms, "unit": f"batched iterations/s (batch={B})", "n_gpus": 1,
            "steps": steps, "warmup": warmup, "ms_per_step": ms,
            "higher_is_better": True, "dtype": dtype, "data": "synthetic x0 ~ U(-1,1)",
-           "config": {"workload": (f"the RBD example's costs on the shipped {pr.n_joints}-DoF arm (fixed base, "
-                                   f"gravity {[float(v) for v in pr.chain.gravity]})" if six else
+           "config": {"workload": (f"the RBD example's costs on {what} (fixed base, "
+                                   f"gravity {[float(v) for v in pr.chain.gravity]})" if tiles else
                                    "BASELINE config 5 (RBD_2_link_example, fixed base)"),
                       "batch": B, "T": T, "linearization": lin, "dynamics": s.dynamics_mode,
                       "cost_mode": s.cost_mode,
@@ -176,9 +181,10 @@ def measure(lin="fd", B=2048, T=100, nu=1, dtype="f32", steps=100, warmup=100, d
             base["value"] = base["value"] / B  # trajectory-iterations/s → batched it/s
             base["unit"] = f"batched iterations/s (batch={B})"
         res["cpu_baseline"] = base
-        if six:  # the rate against the C restatement's, from this same run
+        if tiles:  # the rate against the C restatement's, from this same run
             res["ratio_to_cpu_baseline"] = res["value"] / base["value"]
-    res["fit"] = fit_timing(s, x, u)
+    if fit:
+        res["fit"] = fit_timing(s, x, u)
     s.close()
     return res
 
@@ -214,30 +220,42 @@ def main():
     ap.add_argument("--lin", default="fd,dual")
     ap.add_argument("--cpu-budget", type=float, default=10.0)
     ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--robot", default="2dof_arm", choices=["2dof_arm", "6dof_arm"],
-                    help="6dof_arm: every joint driven (nu = 6), --dtype f64 only")
+    ap.add_argument("--robot", default="2dof_arm", choices=["2dof_arm", "6dof_arm", "coupled"],
+                    help="6dof_arm: every joint driven (nu = 6), --dtype f64 only; coupled: "
+                         "coupled_chain_problem(--joints), every joint driven, gravity on, --dtype f64 only")
+    ap.add_argument("--joints", type=int, default=None, choices=[4, 5, 6, 7],
+                    help="coupled: the number of joints")
     ap.add_argument("--gravity", action="store_true", help="6dof_arm: gravity (0, 0, -9.81) on")
     ap.add_argument("--dynamics", default="auto", choices=["auto", "rnea", "closed_form"],
                     help="the chain handle's dynamics evaluator (ilqr_chain_set_dynamics)")
     ap.add_argument("--simple-cost", action="store_true",
-                    help="6dof_arm: cost_functions.jl's task-space costs (ilqr_chain_set_task_costs) in place "
+                    help="6dof_arm, coupled: cost_functions.jl's task-space costs (ilqr_chain_set_task_costs) in place "
                          "of the joint-space ones; no CPU baseline (the C restatement has the joint costs)")
+    ap.add_argument("--no-fit", action="store_true",
+                    help="skip the end-to-end ChainSolver.fit timing (90 synchronous fits)")
     args = ap.parse_args()
     base = None
     problem = None
+    robot = None
+    if args.robot != "2dof_arm" and args.dtype != "f64":
+        ap.error(f"--robot {args.robot} runs --dtype f64 only (its iteration kernels are fp64)")
+    if (args.joints is not None) != (args.robot == "coupled"):
+        ap.error("--robot coupled and --joints N (4, 5, 6 or 7) go together")
     if args.robot == "6dof_arm":
-        if args.dtype != "f64":
-            ap.error("--robot 6dof_arm runs --dtype f64 only (its iteration kernels are fp64)")
         problem = rbd_6dof_problem(gravity=args.gravity)
     elif args.gravity:
-        ap.error("--gravity goes with --robot 6dof_arm")
-    if args.simple_cost and args.robot != "6dof_arm":
-        ap.error("--simple-cost goes with --robot 6dof_arm")
+        ap.error("--gravity goes with --robot 6dof_arm (the coupled chain has it on)")
+    if args.robot == "coupled":
+        problem = coupled_chain_problem(args.joints)
+        robot = f"coupled_chain_problem({args.joints})"
+    if args.simple_cost and args.robot == "2dof_arm":
+        ap.error("--simple-cost goes with --robot 6dof_arm or coupled")
     for lin in args.lin.split(","):
         res = measure(lin, args.batch, args.T, args.nu, args.dtype, args.steps, args.warmup,
                       dynamics=args.dynamics,
                       cpu_budget=None if args.no_cpu or args.simple_cost else args.cpu_budget, base=base,
-                      problem=problem, simple_cost=args.simple_cost)
+                      problem=problem, simple_cost=args.simple_cost, robot=robot,
+                      fit=not args.no_fit)
         base = res["cpu_baseline"]
         print(json.dumps(res), flush=True)
 
