@@ -13,7 +13,9 @@
 //  * linearize_dynamics (src/backward_pass.jl:25-40, ForwardDiff): forward-mode dual
 //    numbers (ILQR_LINEARIZE_DUAL, exact like the reference) or central finite
 //    differences (ILQR_LINEARIZE_CENTRAL_FD, what BASELINE config 5 names), one lane
-//    per (trajectory, step, direction).
+//    per (trajectory, step, direction); on the tiles path also ILQR_LINEARIZE_ANALYTIC, the
+//    duals' Jacobians from the tangent of the Newton-Euler pass at fixed q̈
+//    (chain_linearize_analytic_kernel).
 //  * immediate_cost / final_cost (:85-116) on the joint rows: Σ qwᵢ(θ*ᵢ−θᵢ)² + Σ rwₖuₖ²
 //    and Σ qfwᵢ(θ*ᵢ−θᵢ)²; their derivatives are the exact constants.
 //  * backward_pass / forward_pass / fit: the Riccati recursion (four trajectories per
@@ -1858,6 +1860,163 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LIN == ILQR
   for (int i = 0; i < NX; ++i) out[i * ld] = col[i];
 }
 
+// ILQR_LINEARIZE_ANALYTIC: the exact Jacobians without differentiating M or the solve. For
+// q̈ = M(q)⁻¹(τ − b(q, q̇)), ID(q, q̇, q̈) = M q̈ + b is the Newton-Euler pass and
+//   δq̈ = M⁻¹(δτ − δ[ID(q, q̇, q̈)]),  q̈ held fixed,
+// so a direction costs one tangent pass (rnea<true, true> in DualT<1>) and one solve with the
+// stage's M per RK4 stage, and the stage's primal (M, b, q̈) is the same for the 3·NJ directions
+// of a point (DESIGN.md "The analytic linearisation").
+//
+// Lane map: a point (b, t) is ND = 3·NJ consecutive lanes of one wave, PPW = 64 / ND points
+// per wave (the wave's last 64 − PPW·ND lanes idle along on its first point and store
+// nothing); lane kd of a point carries direction kd of [δx | δu] and stores column kd of
+// [A | B] as chain_linearize_tiles_kernel does. Per stage, lane kd ≤ NJ of the point also runs
+// pass kd of the primal — 0: the bias (q̇, 0, gravity), k + 1: column k of M (0, e_k, no
+// gravity), one uniform rnea<true, true> with per-lane arguments as in the forward group — and
+// the NJ + 1 results reach the point's lanes through a wave-private LDS region. Every lane
+// then eliminates M itself (chain_xdot's elimination), for q̈ and again for δq̈: the second
+// solve reads M from the region again, so keeping the factor over the tangent pass or redoing
+// it is the compiler's choice (it keeps the multipliers: six reciprocals per stage at six joints).
+// No lane leaves early and there is no workgroup barrier: a lane past the last point or on
+// a stopped trajectory computes on a clamped point and skips the store.
+// One wave per SIMD: the tangent pass keeps R, fn and ff as duals (180 doubles at six joints;
+// profiles/chain_analytic/resource_usage.txt). The chain constants stay kernel arguments:
+// read from LDS instead (chain_consts_to_lds) the SGPR-spill v_readlanes go (10,004 → 8,149
+// instructions per stage at six joints) but the constants then compete for VGPRs, scratch
+// doubles to 1.4 KB per lane and the kernel is slower at five to seven joints (8.67 → 14.67 ms
+// at six; profiles/chain_analytic/lds_constants.txt).
+constexpr int CHAIN_ANALYTIC_WAVES = 1;
+// o = M⁻¹ r, M's column k at m[(k + 1)·NJ ..] (the exchange region; m[0 .. NJ) is the bias)
+template <int NJ>
+__device__ __forceinline__ void chain_analytic_solve(const double* m, double (&r)[NJ], double (&o)[NJ]) {
+  double M[NJ][NJ];
+#pragma unroll
+  for (int k = 0; k < NJ; ++k)
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) M[i][k] = m[(k + 1) * NJ + i];
+#pragma unroll
+  for (int k = 0; k < NJ; ++k) {
+    const double inv = crecip(M[k][k]);
+#pragma unroll
+    for (int i = k + 1; i < NJ; ++i) {
+      const double l = M[i][k] * inv;
+#pragma unroll
+      for (int j = k + 1; j < NJ; ++j) M[i][j] = M[i][j] - l * M[k][j];
+      r[i] = r[i] - l * r[k];
+    }
+  }
+#pragma unroll
+  for (int i = NJ - 1; i >= 0; --i) {
+    double acc = r[i];
+#pragma unroll
+    for (int j = i + 1; j < NJ; ++j) acc = acc - M[i][j] * o[j];
+    o[i] = acc * crecip(M[i][i]);
+  }
+}
+
+template <int NJ>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CHAIN_ANALYTIC_WAVES))) void chain_linearize_analytic_kernel(
+    ChainK<double, NJ> P, int B, int T, const double* __restrict__ x, const double* __restrict__ u,
+    const int32_t* __restrict__ status, double* __restrict__ A, double* __restrict__ Bm) {
+  using V = double;
+  using D = DualT<1, V>;
+  constexpr int NU = NJ, NX = 2 * NJ, ND = NX + NU, PPW = 64 / ND, NE = (NJ + 1) * NJ;
+  static_assert(3 * NJ <= 64, "a point's directions are lanes of one wave");
+  __shared__ V xch[4][PPW][NE];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int pw_ = lane / ND;
+  const bool spare = pw_ >= PPW;  // the wave's lanes past its last point
+  const int pw = spare ? 0 : pw_;
+  const int kd = lane - pw_ * ND;
+  const size_t npt = (size_t)B * T;
+  size_t bt = ((size_t)blockIdx.x * 4 + wave) * PPW + pw;
+  bool store = !spare && bt < npt;
+  if (bt >= npt) bt = npt - 1;  // reads stay in range
+  const int b = (int)(bt / T), t = (int)(bt - (size_t)b * T);
+  if (status && status[b] != ILQR_TRAJ_OK) store = false;
+  const V* xb = x + ((size_t)b * (T + 1) + t) * NX;
+  const V* ub = u + bt * NU;
+  V* reg = xch[wave][pw];
+  const bool pass = !spare && kd <= NJ;  // this lane's primal pass is one of the point's NJ + 1
+  V xs[NX], us[NU], kp[NX], dkp[NX], acc[NX];
+#pragma unroll
+  for (int i = 0; i < NX; ++i) {
+    xs[i] = xb[i];
+    kp[i] = V(0);
+    dkp[i] = V(0);
+    acc[i] = V(0);
+  }
+#pragma unroll
+  for (int i = 0; i < NU; ++i) us[i] = ub[i];
+  // the stages as one loop: y_s = x + a_s k_{s−1} with a = 0, ½, ½, 1 (k₀ = 0) and the sum
+  // ((δk₁ + 2δk₂) + 2δk₃) + δk₄ accumulated in chain_rk4's association
+#pragma unroll 1
+  for (int s = 0; s < 4; ++s) {
+    const V a = s == 0 ? V(0) : s == 3 ? V(1) : V(0.5);
+    const V wgt = (s == 1 || s == 2) ? V(2) : V(1);
+    V y[NX], dy[NX], c[NJ], sn[NJ];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      y[i] = xs[i] + a * kp[i];
+      dy[i] = (i == kd ? V(1) : V(0)) + a * dkp[i];
+    }
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) scs(y[i], sn[i], c[i]);
+    {  // the primal: pass kd of the point
+      V qd[NJ], qdd[NJ], tau[NJ];
+#pragma unroll
+      for (int i = 0; i < NJ; ++i) {
+        qd[i] = kd == 0 ? y[NJ + i] : V(0);
+        qdd[i] = kd == i + 1 ? V(1) : V(0);
+      }
+      rnea<true, true>(P, c, sn, qd, qdd, tau, kd == 0 ? V(1) : V(0));
+      wave_lds_fence();  // the previous stage's reads of the region are done
+      if (pass) {
+#pragma unroll
+        for (int i = 0; i < NJ; ++i) reg[kd * NJ + i] = tau[i];
+      }
+      wave_lds_fence();
+    }
+    V qdd[NJ], r[NJ];
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) r[i] = us[i] - reg[i];
+    chain_analytic_solve<NJ>(reg, r, qdd);
+    // δ[ID(q, q̇, q̈)] along this lane's direction
+    V dqdd[NJ];
+    {
+      D cD[NJ], sD[NJ], qdD[NJ], qddD[NJ], tauD[NJ];
+#pragma unroll
+      for (int i = 0; i < NJ; ++i) {
+        cD[i].v = c[i];
+        cD[i].d[0] = -sn[i] * dy[i];
+        sD[i].v = sn[i];
+        sD[i].d[0] = c[i] * dy[i];
+        qdD[i].v = y[NJ + i];
+        qdD[i].d[0] = dy[NJ + i];
+        qddD[i] = D(qdd[i]);
+      }
+      rnea<true, true>(P, cD, sD, qdD, qddD, tauD);
+#pragma unroll
+      for (int i = 0; i < NJ; ++i) r[i] = (NX + i == kd ? V(1) : V(0)) - tauD[i].d[0];
+    }
+    chain_analytic_solve<NJ>(reg, r, dqdd);
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) {
+      kp[i] = P.dt * y[NJ + i];
+      kp[NJ + i] = P.dt * qdd[i];
+      dkp[i] = P.dt * dy[NJ + i];
+      dkp[NJ + i] = P.dt * dqdd[i];
+    }
+#pragma unroll
+    for (int i = 0; i < NX; ++i) acc[i] = acc[i] + wgt * dkp[i];
+  }
+  if (!store) return;
+  V* out = kd < NX ? A + bt * NX * NX + kd : Bm + bt * NX * NU + (kd - NX);
+  const int ld = kd < NX ? NX : NU;
+#pragma unroll
+  for (int i = 0; i < NX; ++i) out[i * ld] = (i == kd ? V(1) : V(0)) + (V(1) / V(6)) * acc[i];
+}
+
 // the joint-space cost (RBD_helper_functions.jl:85-116) of an NJ-joint chain
 template <int NJ>
 struct ChainCostK {
@@ -2619,7 +2778,9 @@ double chain_task_build(const ilqr_chain& c, int body, const double pt[3], const
   return err / reach;
 }
 
-// h->lin as a compile-time constant: fn(std::integral_constant<int, LIN>{})
+// h->lin as a compile-time constant: fn(std::integral_constant<int, LIN>{}), for the kernels
+// that carry both modes (ILQR_LINEARIZE_ANALYTIC is a kernel of its own, tiles path only:
+// ChainTilesOps::linearize branches to it before coming here)
 template <class Fn>
 hipError_t with_lin(const ilqr_chain_handle* h, Fn&& fn) {
   if (h->lin == ILQR_LINEARIZE_DUAL) return fn(std::integral_constant<int, ILQR_LINEARIZE_DUAL>{});
@@ -2771,6 +2932,12 @@ struct ChainTilesOps {
   // A and B of trajectories with status OK (st null: all)
   static hipError_t linearize(ilqr_chain_handle* h, const V* x, const V* u, const int32_t* st, V* A, V* Bm) {
     const auto P = chain_consts<V, NJ>(h->chain);
+    if (h->lin == ILQR_LINEARIZE_ANALYTIC) {  // 64 / (NX + NU) points per wave, four waves
+      const size_t per_wg = 4 * (64 / (NX + NU)), wgs = ((size_t)h->batch * h->T + per_wg - 1) / per_wg;
+      ilqr::chain_linearize_analytic_kernel<NJ><<<dim3((unsigned)wgs), 256, 0, h->stream>>>(
+          P, h->batch, h->T, x, u, st, A, Bm);
+      return hipGetLastError();
+    }
     const size_t lanes = (size_t)h->batch * h->T * (NX + NU);
     const dim3 grid((unsigned)((lanes + 255) / 256));
     return with_lin(h, [&](auto lin) {
@@ -3020,10 +3187,17 @@ ilqr_status ilqr_chain_create(ilqr_chain_handle** out, int device, const ilqr_ch
   if (chain->n_joints > ILQR_CHAIN_MAX_JOINTS || !(chain->nu == chain->n_joints || chain->nu == 1))
     return ILQR_ERR_BAD_DIMS;
   if (dtype != ILQR_F32 && dtype != ILQR_F64) return ILQR_ERR_BAD_ARG;
-  if (linearization != ILQR_LINEARIZE_DUAL && linearization != ILQR_LINEARIZE_CENTRAL_FD)
+  if (linearization != ILQR_LINEARIZE_DUAL && linearization != ILQR_LINEARIZE_CENTRAL_FD &&
+      linearization != ILQR_LINEARIZE_ANALYTIC)
     return ILQR_ERR_BAD_ARG;
   if (!(chain->dt > 0.0)) return ILQR_ERR_BAD_ARG;
   if (!dyn_supported(chain->n_joints, chain->nu)) return ILQR_ERR_UNSUPPORTED;
+  if (linearization == ILQR_LINEARIZE_ANALYTIC &&
+      !(tiles_shape(chain->n_joints, chain->nu) && dtype == ILQR_F64)) {
+    g_chain_error = "ilqr_chain_create: ILQR_LINEARIZE_ANALYTIC is the tiles path's (4 to 7 joints, "
+                    "every joint driven, ILQR_F64)";
+    return ILQR_ERR_UNSUPPORTED;
+  }
   CH_TRY(hipSetDevice(device));
   auto* h = new ilqr_chain_handle;
   h->device = device;

@@ -54,6 +54,7 @@ F64 = 0
 F32 = 1
 LINEARIZE_DUAL = 0
 LINEARIZE_CENTRAL_FD = 1
+LINEARIZE_ANALYTIC = 2   # chains of 4 to 7 joints in F64 (the tiles path)
 CHAIN_DYN_AUTO = 0          # ilqr_chain_dynamics_mode
 CHAIN_DYN_RNEA = 1
 CHAIN_DYN_CLOSED_FORM = 2

@@ -834,6 +834,7 @@ const ILQR_F64 = Int32(0)
 const ILQR_F32 = Int32(1)
 const ILQR_LINEARIZE_DUAL = Int32(0)
 const ILQR_LINEARIZE_CENTRAL_FD = Int32(1)
+const ILQR_LINEARIZE_ANALYTIC = Int32(2)   # chains of 4 to 7 joints in Float64 only
 
 struct Chain                 # ilqr_chain (include/ilqr.h), ILQR_CHAIN_MAX_JOINTS = 8
     n_joints::Int32; nu::Int32; dt::Float64; gravity::NTuple{3,Float64}
@@ -923,7 +924,11 @@ const CHAIN_CACHE = Dict{Tuple{Chain,Int,Int,DataType,Int32,Int32,Union{Nothing,
 
 Batched fit of the chain family; x_init (nx, T+1, batch), u_init (nu, T, batch) as
 Array{Float32,3} (fp32, BASELINE config 5) or Array{Float64,3}: the element type picks
-the device precision, as the reference's generic Julia code would. `dynamics` picks the
+the device precision, as the reference's generic Julia code would. `linearization` is
+ILQR_LINEARIZE_DUAL (forward-mode duals, ForwardDiff's algorithm; the default),
+ILQR_LINEARIZE_CENTRAL_FD (central differences) or, for 4 to 7 joints in Float64,
+ILQR_LINEARIZE_ANALYTIC (the duals' exact Jacobians from δq̈ = M⁻¹(δτ − δ[ID(q, q̇, q̈)]),
+about twelve times faster to form at six joints; ilqr_chain_create refuses it elsewhere). `dynamics` picks the
 2-joint evaluator (AUTO: the closed form sampled from the Newton-Euler recursion at
 creation; RNEA: the recursion itself). `costs = simple_costs(…)` replaces the chain's
 joint-space costs with cost_functions.jl's pair (2-joint chains: the closed form,

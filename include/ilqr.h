@@ -304,7 +304,13 @@ ilqr_status ilqr_fit_ex(ilqr_handle* h, const ilqr_problem* p, const ilqr_option
  * with τ = u (nu = n_joints) or τ = [u₁, 0, …] (nu = 1). Arrays use the layout
  * above in the handle's dtype (ILQR_F32 or ILQR_F64), costs included; the
  * derivatives of dynamicsf are forward-mode duals (ForwardDiff's algorithm,
- * ILQR_LINEARIZE_DUAL) or central differences (ILQR_LINEARIZE_CENTRAL_FD).
+ * ILQR_LINEARIZE_DUAL), central differences (ILQR_LINEARIZE_CENTRAL_FD) or, for chains of
+ * 4 to 7 joints in ILQR_F64, ILQR_LINEARIZE_ANALYTIC: the same exact Jacobians as the duals
+ * from δq̈ = M⁻¹(δτ − δ[ID(q, q̇, q̈)]) with q̈ held fixed — one tangent Newton-Euler pass and
+ * one solve with the stage's M per RK4 stage and direction, the stage's M, bias and q̈
+ * computed once per (trajectory, step) — faster than either (DESIGN.md has the table); it is
+ * honoured by every call that linearises (linearize, backward, iterate, fit, fit_ex; joint
+ * or task costs). The default everywhere stays ILQR_LINEARIZE_DUAL.
  * Compiled shapes (ilqr_chain_supported_dtype): the 2-joint arm with nu = 1 or 2 in
  * either dtype, and serial chains of n_joints = nu = 4, 5, 6 or 7 (the 6-DoF arm, a 7-DoF
  * manipulator; every joint driven) in ILQR_F64 — every entry point, both linearisations,
@@ -329,7 +335,11 @@ ilqr_status ilqr_fit_ex(ilqr_handle* h, const ilqr_problem* p, const ilqr_option
 #define ILQR_CHAIN_MAX_JOINTS 8
 
 typedef enum { ILQR_F64 = 0, ILQR_F32 = 1 } ilqr_dtype;
-typedef enum { ILQR_LINEARIZE_DUAL = 0, ILQR_LINEARIZE_CENTRAL_FD = 1 } ilqr_linearization;
+typedef enum {
+  ILQR_LINEARIZE_DUAL = 0,
+  ILQR_LINEARIZE_CENTRAL_FD = 1,
+  ILQR_LINEARIZE_ANALYTIC = 2 /* chains of 4 to 7 joints in ILQR_F64 only */
+} ilqr_linearization;
 
 typedef struct {
   int32_t n_joints;    /* revolute joints, root to tip (ilqr_amd.urdf.parse_urdf)          */
@@ -360,6 +370,14 @@ int ilqr_chain_supported(int n_joints, int nu);
  * chain, an invalid dtype. */
 int ilqr_chain_supported_dtype(int n_joints, int nu, int32_t dtype);
 const char* ilqr_chain_last_error(void);
+/* Refusals, in this order, before any device call: NULL out / chain → ILQR_ERR_BAD_ARG;
+ * T, batch, n_joints or nu ≤ 0, more than ILQR_CHAIN_MAX_JOINTS joints, nu other than
+ * n_joints or 1 → ILQR_ERR_BAD_DIMS; a dtype other than ILQR_F32 / ILQR_F64, a
+ * linearization other than the three ilqr_linearization values, dt ≤ 0 →
+ * ILQR_ERR_BAD_ARG; a shape without kernels → ILQR_ERR_UNSUPPORTED; then
+ * ILQR_LINEARIZE_ANALYTIC on a handle that would not iterate on the tiles path (any 2-joint
+ * chain, 4 to 7 joints in ILQR_F32) → ILQR_ERR_UNSUPPORTED with a sentence in
+ * ilqr_chain_last_error. */
 ilqr_status ilqr_chain_create(ilqr_chain_handle** out, int device, const ilqr_chain* chain, int T,
                               int batch, int32_t dtype, int32_t linearization);
 ilqr_status ilqr_chain_destroy(ilqr_chain_handle* h);

@@ -128,7 +128,8 @@ def measure(lin="fd", B=2048, T=100, nu=1, dtype="f32", steps=100, warmup=100, d
     # (pricing it on the recursion's 16x larger count put the linearisation above peak)
     f_ref = FL.chain_dynamics_flops(pr)
     f_rk4 = FL.chain_closed_form_flops(pr.nu) if s.dynamics_mode == "closed_form" else f_ref
-    lin_fl = (f_rk4 * FL.dual_factor(nd) if lin == "dual" else 2 * nd * f_rk4 + nd * pr.nx) * T * B
+    lin_fl = (f_rk4 * FL.dual_factor(nd) if lin == "dual" else
+              FL.chain_analytic_flops(pr) if lin == "analytic" else 2 * nd * f_rk4 + nd * pr.nx) * T * B
     ric_fl = FL.riccati_flops_per_step(pr.nx, pr.nu) * T * B
     fw_fl = FL.forward_flops_per_step(pr.nx, pr.nu, f_rk4) * T * B
     peak = PEAK_TFLOPS[dtype]
@@ -217,7 +218,9 @@ def main():
     ap.add_argument("--nu", type=int, default=1, choices=[1, 2],
                     help="1 = BASELINE config 5 as stated; 2 = both joints actuated")
     ap.add_argument("--dtype", default="f32", choices=["f32", "f64"])
-    ap.add_argument("--lin", default="fd,dual")
+    ap.add_argument("--lin", default="fd,dual",
+                    help="comma-separated: fd, dual, analytic (analytic: --robot 6dof_arm or coupled, f64; "
+                         "the CPU restatement has no analytic leg, so its result carries no cpu_baseline)")
     ap.add_argument("--cpu-budget", type=float, default=10.0)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--robot", default="2dof_arm", choices=["2dof_arm", "6dof_arm", "coupled"],
@@ -253,10 +256,11 @@ def main():
     for lin in args.lin.split(","):
         res = measure(lin, args.batch, args.T, args.nu, args.dtype, args.steps, args.warmup,
                       dynamics=args.dynamics,
-                      cpu_budget=None if args.no_cpu or args.simple_cost else args.cpu_budget, base=base,
+                      cpu_budget=None if args.no_cpu or args.simple_cost or lin == "analytic" else args.cpu_budget,
+                      base=base,
                       problem=problem, simple_cost=args.simple_cost, robot=robot,
                       fit=not args.no_fit)
-        base = res["cpu_baseline"]
+        base = res["cpu_baseline"] or base
         print(json.dumps(res), flush=True)
 
 

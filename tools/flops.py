@@ -64,6 +64,22 @@ def chain_dynamics_flops(problem):
     return Counter.n
 
 
+def chain_analytic_flops(problem):
+    """FLOPs of the analytic linearisation (ILQR_LINEARIZE_ANALYTIC) at one point: per RK4 stage
+    the primal once (a quarter of chain_dynamics_flops) and, for each of the nx + nu directions,
+    the tangent of one Newton-Euler pass with velocities and gravity (dual_factor(1) − 1 = 2
+    times the pass) and the two triangular solves with the stage's factor (2n²)."""
+    from oracle import rbd
+    m = rbd.ChainModel(problem.chain, problem.dt)
+    n = problem.n_joints
+    q = [Flop(0.3 * (i + 1)) for i in range(n)]
+    Counter.n = 0
+    m.rnea(q, q, q, gravity=True)
+    f_pass = Counter.n
+    nd = problem.nx + problem.nu
+    return chain_dynamics_flops(problem) + 4 * nd * ((dual_factor(1) - 1) * f_pass + 2 * n * n)
+
+
 # the 2-link arm's dynamicsf as the device functor evaluates it (ilqr_twolink.hip:
 # continuous_dynamics + rk4, the formulas of 2_link_helper_functions.jl:29-79)
 def twolink_dynamics_flops(nu=2):
