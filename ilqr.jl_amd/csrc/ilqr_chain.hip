@@ -34,6 +34,10 @@
 //    32-lane forward group (ChainTaskK, ilqr_chain_set_task_costs,
 //    ilqr_chain_final_cost_quadratize; fp64). ilqr_chain_set_simple_costs keeps refusing
 //    more than two joints, and an fp32 handle of more than two joints answers dynamics only.
+//  * a goal per trajectory on the tiles path (ilqr_chain_set_joint_targets: θ*,
+//    ilqr_chain_set_task_targets: final_target): the handle's copy of the rows, read by the
+//    ChainGoalRows instantiations of the cost tiles, the task quadratization and the forward
+//    kernels; a handle without rows launches the instantiations it always did.
 // Layout as the other families (include/ilqr.h): x (B, T+1, nx), u/d (B, T, nu),
 // K (B, T, nu, nx), trajectory slowest, nx = 2·n_joints.
 #include <hip/hip_runtime.h>
@@ -2023,12 +2027,24 @@ struct ChainCostK {
   double tgt[NJ], qw[NJ], rw[NJ], qfw[NJ];
 };
 
+// A goal per trajectory (ilqr_chain_set_joint_targets: NJ doubles a row, θ*;
+// ilqr_chain_set_task_targets: 3 doubles a row, final_target): the handle's copy of the rows.
+// Every kernel that reads a goal takes it as a trailing pack beside its constants — empty for
+// a handle without rows, whose instantiations, kernel arguments and code stay what they were
+// (the TaskK pack of the forward kernels below) — and, with it, reads row b where it read
+// the constant: the same expression in the same order, another source.
+struct ChainGoalRows {
+  const double* rows;
+};
+__device__ __forceinline__ const double* goal_rows(const ChainGoalRows& g) { return g.rows; }
+
 // The cost tiles that change with (x, u), the terms chain_backward4_wave forms for two joints
 // (immediate_cost_quadratization :81-109, final_cost_quadratization :134-153):
 // lx = −2qw(θ* − θ) on the joint rows, lu = 2rw·u, lfx = −2qfw(θ* − θ_N).
 // One lane per element: (b, t ≤ T, e < NX + NU), t = T the terminal row.
-template <int NJ, int NU>
-__global__ __launch_bounds__(256) void chain_cost_tiles_kernel(ChainCostK<NJ> C, int B, int T,
+// Goal: none (θ* = C.tgt) or ChainGoalRows (θ* = row b).
+template <int NJ, int NU, class... Goal>
+__global__ __launch_bounds__(256) void chain_cost_tiles_kernel(ChainCostK<NJ> C, Goal... G, int B, int T,
                                                                const double* __restrict__ x,
                                                                const double* __restrict__ u,
                                                                const int32_t* __restrict__ status,
@@ -2046,6 +2062,9 @@ __global__ __launch_bounds__(256) void chain_cost_tiles_kernel(ChainCostK<NJ> C,
 #pragma unroll
   for (int i = 1; i < NJ; ++i)
     if (i == j) { tgt = C.tgt[i]; qw = C.qw[i]; rw = C.rw[i]; qfw = C.qfw[i]; }
+  static_assert((std::is_same_v<Goal, ChainGoalRows> && ...) && sizeof...(Goal) <= 1, "Goal: none or ChainGoalRows");
+  if constexpr (sizeof...(Goal) == 1)
+    if (e < NJ) tgt = goal_rows(G...)[(size_t)b * NJ + e];
   if (e < NX) {
     const double xe = x[((size_t)b * (T + 1) + t) * NX + e];
     if (t == T) lfx[(size_t)b * NX + e] = e < NJ ? -2.0 * qfw * (tgt - xe) : 0.0;
@@ -2223,9 +2242,11 @@ __device__ void chain_task_quad_fk(const ChainK<double, NJ>& P, const ChainTaskK
 //    whose status is not OK are skipped like chain_cost_tiles_kernel's;
 //  * ilqr_chain_final_cost_quadratize (xstride = NX), any output null; in the joint mode
 //    (joint = 1) the handle's joint-space final cost Σ qfwᵢ(θ*ᵢ − θᵢ)² instead.
-template <int NJ>
-__global__ __launch_bounds__(64) void chain_task_quad_kernel(ChainK<double, NJ> P, ChainTaskK C, int joint, int n,
-                                                             const double* __restrict__ x, size_t xstride,
+// Goal: none, or ChainGoalRows — the goal of state s is row s (NJ doubles with joint = 1,
+// 3 otherwise; the caller has n ≤ the rows it holds).
+template <int NJ, class... Goal>
+__global__ __launch_bounds__(64) void chain_task_quad_kernel(ChainK<double, NJ> P, ChainTaskK C, Goal... G, int joint,
+                                                             int n, const double* __restrict__ x, size_t xstride,
                                                              const int32_t* __restrict__ status,
                                                              double* __restrict__ cost, double* __restrict__ grad,
                                                              double* __restrict__ hess) {
@@ -2237,16 +2258,25 @@ __global__ __launch_bounds__(64) void chain_task_quad_kernel(ChainK<double, NJ> 
   double q[NJ], c, g[NJ], H[NJ][NJ];
 #pragma unroll
   for (int i = 0; i < NJ; ++i) q[i] = xb[i];
+  static_assert((std::is_same_v<Goal, ChainGoalRows> && ...) && sizeof...(Goal) <= 1, "Goal: none or ChainGoalRows");
+  constexpr bool ROWS = sizeof...(Goal) == 1;
   if (joint) {
     c = 0.0;
 #pragma unroll
     for (int i = 0; i < NJ; ++i) {
-      const double e = P.tgt[i] - q[i];
+      double tg = P.tgt[i];
+      if constexpr (ROWS) tg = goal_rows(G...)[(size_t)b * NJ + i];
+      const double e = tg - q[i];
       c = fma(P.qfw[i] * e, e, c);
       g[i] = -2.0 * P.qfw[i] * e;
 #pragma unroll
       for (int j = i; j < NJ; ++j) H[i][j] = i == j ? 2.0 * P.qfw[i] : 0.0;
     }
+  } else if constexpr (ROWS) {
+    ChainTaskK Cb = C;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) Cb.t[k] = goal_rows(G...)[(size_t)b * 3 + k];
+    chain_task_quad_fk<NJ>(P, Cb, q, c, g, H);
   } else {
     chain_task_quad_fk<NJ>(P, C, q, c, g, H);
   }
@@ -2290,8 +2320,15 @@ static_assert(ChainStage<7, 7>::WORDS == 5 && ChainStage<7, 7>::SIZE == 160, "se
 // TASK: the costs of a task mode (ℓ = Σū², ℓ_f the task cost C of x̄_N, every lane of the
 // group evaluating it on its own copy of x̄_N by the same code: the same bits in all 32) in
 // place of the joint-space ones, chosen at compile time so that the joint-cost
-// instantiations keep their instruction streams
-template <int NJ, int NU, bool TASK = false>
+// instantiations keep their instruction streams.
+// ROWS: the goal of trajectory b is row b of `goal` (NJ doubles, θ*; 3 with TASK, final_target)
+// in place of P.tgt / C.t, likewise a compile-time choice. The row rides in the stage's unused
+// tail, which every lane count leaves (12, 21, 20 and 27 words for 4..7 joints): the lanes
+// whose words fall past the record re-read K's first word at every step anyway, so with ROWS
+// the first NG of those words read the row instead (stride 0) and the hand-off delivers it
+// to the group at stage[N_IN ..) — no register beyond what the shared-goal code holds, which
+// at seven joints already fills both register files.
+template <int NJ, int NU, bool TASK = false, bool ROWS = false, class... Goal>
 __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P, double* __restrict__ stage,
                                                      int b, int T, const double* __restrict__ x,
                                                      const double* __restrict__ u,
@@ -2300,13 +2337,17 @@ __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P
                                                      const double* __restrict__ Kg, double prev_cost,
                                                      double* __restrict__ xnew, double* __restrict__ unew,
                                                      double* du2_out, const LSParams& ls,
-                                                     const ChainTaskK& C = ChainTaskK{}) {
+                                                     const ChainTaskK& C = ChainTaskK{}, const Goal&... G) {
   using V = double;
+  static_assert((std::is_same_v<Goal, ChainGoalRows> && ...) && sizeof...(Goal) == (ROWS ? 1 : 0),
+                "Goal: ChainGoalRows with ROWS, else none (the shared-goal instantiations keep their signature)");
   constexpr int NX = 2 * NJ, NK = NU * NX;
   constexpr int O_X = NK, O_XT = O_X + NX, O_U = O_XT + NJ, O_D = O_U + NU, N_IN = O_D + NU;
   constexpr int NW = ChainStage<NJ, NU>::WORDS;
   static_assert(N_IN == ChainStage<NJ, NU>::N_IN && N_IN <= ChainStage<NJ, NU>::SIZE && NX + NU <= CH32_LANES,
                 "a step's inputs in NW words per lane, x̄ and ū stored by one lane each");
+  constexpr int NG = ROWS ? (TASK ? 3 : NJ) : 0, O_G = N_IN;  // the goal row in the stage's tail
+  static_assert(N_IN + NG <= ChainStage<NJ, NU>::SIZE, "the goal row fits the stage's unused tail");
   const int l32 = threadIdx.x & (CH32_LANES - 1);
   const V* xb0 = x + (size_t)b * (T + 1) * NX;
   const V* ub0 = u + (size_t)b * T * NU;
@@ -2329,6 +2370,9 @@ __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P
     else if (e < O_U) { src[k] = xt0 + (e - O_XT); str[k] = NX; }
     else if (e < O_D) { src[k] = ub0 + (e - O_U); str[k] = NU; }
     else if (e < N_IN) { src[k] = d0 + (e - O_D); str[k] = NU; }
+    else if constexpr (ROWS) {  // stride 0: the row at every step
+      if (e < O_G + NG) src[k] = goal_rows(G...) + (size_t)b * NG + (e - O_G);
+    }
   }
   V alpha = V(ls.alpha0);
   ChainFwdOut<V> out{V(0), 0, 0};
@@ -2373,8 +2417,13 @@ __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P
       } else {
 #pragma unroll
         for (int i = 0; i < NJ; ++i) {
-          const V e = P.tgt[i] - fma(-xtw, stage[O_XT + i], xb[i]);
-          lk = fma(P.qw[i] * e, e, lk);
+          if constexpr (ROWS) {
+            const V e = stage[O_G + i] - fma(-xtw, stage[O_XT + i], xb[i]);
+            lk = fma(P.qw[i] * e, e, lk);
+          } else {
+            const V e = P.tgt[i] - fma(-xtw, stage[O_XT + i], xb[i]);
+            lk = fma(P.qw[i] * e, e, lk);
+          }
         }
 #pragma unroll
         for (int a = 0; a < NU; ++a) lk = fma(P.rw[a] * ubar[a], ubar[a], lk);
@@ -2410,12 +2459,24 @@ __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P
 #pragma unroll
       for (int i = 0; i < NJ; ++i) q[i] = xb[i];
       chain_point_fk<NJ>(P, C, q, pw);
-      lf = chain_task_value(C, pw);
+      if constexpr (ROWS) {  // the last step's hand-off left the row in the stage
+        ChainTaskK Cb = C;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) Cb.t[k] = stage[O_G + k];
+        lf = chain_task_value(Cb, pw);
+      } else {
+        lf = chain_task_value(C, pw);
+      }
     } else {
 #pragma unroll
       for (int i = 0; i < NJ; ++i) {
-        const V e = P.tgt[i] - xb[i];
-        lf = fma(P.qfw[i] * e, e, lf);
+        if constexpr (ROWS) {
+          const V e = stage[O_G + i] - xb[i];
+          lf = fma(P.qfw[i] * e, e, lf);
+        } else {
+          const V e = P.tgt[i] - xb[i];
+          lf = fma(P.qfw[i] * e, e, lf);
+        }
       }
     }
     cost += lf;
@@ -2429,6 +2490,18 @@ __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P
   }
   if (du2_out) *du2_out = du2;
   return out;
+}
+
+// … with the joint-space costs and a goal per trajectory: the rows where the task constants go
+template <int NJ, int NU, bool TASK, bool ROWS>
+__device__ __forceinline__ ChainFwdOut<double> chain_forward_group32(
+    const ChainK<double, NJ>& P, double* __restrict__ stage, int b, int T, const double* __restrict__ x,
+    const double* __restrict__ u, const double* __restrict__ xtraj, const double* __restrict__ dg,
+    const double* __restrict__ Kg, double prev_cost, double* __restrict__ xnew, double* __restrict__ unew,
+    double* du2_out, const LSParams& ls, const ChainGoalRows& G) {
+  static_assert(!TASK && ROWS, "the joint-space costs of a handle with a goal per trajectory");
+  return chain_forward_group32<NJ, NU, false, true>(P, stage, b, T, x, u, xtraj, dg, Kg, prev_cost, xnew, unew, du2_out,
+                                                    ls, ChainTaskK{}, G);
 }
 
 constexpr int CH32_WG = 64;  // two trajectories per workgroup (one wave)
@@ -2446,18 +2519,33 @@ constexpr size_t kernarg_bytes() {
 constexpr size_t HIP_KERNARG_LIMIT = 4096;
 
 // The two forward kernels. TaskK is empty (the joint-space cost) or ChainTaskK (a task mode:
-// the TASK instantiation of the group, the task cost's constants one more kernel argument).
-// As a pack it adds nothing to the joint-cost kernels' argument list, so both modes keep the
-// kernel arguments, and with them the code, that each had as a kernel written out. A pack in
-// the middle of the list is never deduced: every launch spells out <NJ, NU> or
-// <NJ, NU, ChainTaskK>.
+// the TASK instantiation of the group, the task cost's constants one more kernel argument),
+// either followed by ChainGoalRows (a goal per trajectory: the ROWS instantiation, the rows'
+// pointer one more argument). As a pack it adds nothing to the joint-cost kernels' argument
+// list, so every mode keeps the kernel arguments, and with them the code, that each had as a
+// kernel written out. A pack in the middle of the list is never deduced: every launch spells
+// out <NJ, NU>, <NJ, NU, ChainTaskK>, <NJ, NU, ChainGoalRows> or
+// <NJ, NU, ChainTaskK, ChainGoalRows>.
+template <class X, class... A>
+constexpr int pack_count = (0 + ... + (std::is_same_v<A, X> ? 1 : 0));
+// none | ChainTaskK | ChainGoalRows | ChainTaskK, ChainGoalRows
+template <class... A>
+struct CostPack : std::false_type {};
+template <>
+struct CostPack<> : std::true_type {};
+template <>
+struct CostPack<ChainTaskK> : std::true_type {};
+template <>
+struct CostPack<ChainGoalRows> : std::true_type {};
+template <>
+struct CostPack<ChainTaskK, ChainGoalRows> : std::true_type {};
 template <int NJ, int NU, class... TaskK>
 __global__ __launch_bounds__(CH32_WG) void chain_forward32_kernel(
     ChainK<double, NJ> P, TaskK... C, int B, int T, const double* __restrict__ x, const double* __restrict__ u,
     const double* __restrict__ xtraj, const double* __restrict__ d, const double* __restrict__ K,
     const double* __restrict__ prev_cost, double* __restrict__ xnew, double* __restrict__ unew,
     double* __restrict__ new_cost, int32_t* __restrict__ trials, int32_t* __restrict__ status, LSParams ls) {
-  static_assert((std::is_same_v<TaskK, ChainTaskK> && ...) && sizeof...(TaskK) <= 1, "TaskK: none or ChainTaskK");
+  static_assert(CostPack<TaskK...>::value, "TaskK: none or ChainTaskK, then none or ChainGoalRows");
   static_assert(kernarg_bytes<ChainK<double, NJ>, TaskK..., int, int, const double*, const double*, const double*,
                               const double*, const double*, const double*, double*, double*, double*, int32_t*,
                               int32_t*, LSParams>() <= HIP_KERNARG_LIMIT,
@@ -2470,7 +2558,8 @@ __global__ __launch_bounds__(CH32_WG) void chain_forward32_kernel(
   if (b >= B) return;  // the whole lane group
   const int l32 = threadIdx.x & (CH32_LANES - 1);
   const double pc = prev_cost ? prev_cost[b] : (double)INFINITY;
-  const ChainFwdOut<double> r = chain_forward_group32<NJ, NU, sizeof...(TaskK) == 1>(
+  constexpr bool TASK = pack_count<ChainTaskK, TaskK...> == 1, ROWS = pack_count<ChainGoalRows, TaskK...> == 1;
+  const ChainFwdOut<double> r = chain_forward_group32<NJ, NU, TASK, ROWS>(
       Ps, stage + (threadIdx.x / CH32_LANES) * STAGE, b, T, x, u, xtraj, d, K, pc, xnew, unew, nullptr, ls, C...);
   // every lane of the group: the 32 lanes stride the copy of an exhausted search's inputs
   fwd_finish<2 * NJ, NU>(b, T, r.cost, r.trials, r.accepted, x, u, xnew, unew, l32, CH32_LANES, new_cost, trials,
@@ -2485,7 +2574,7 @@ __global__ __launch_bounds__(CH32_WG) void chain_iter_forward32_kernel(ChainK<do
                                                                      ChainIter<double> a,
                                                                      const int32_t* __restrict__ bstatus,
                                                                      LSParams ls) {
-  static_assert((std::is_same_v<TaskK, ChainTaskK> && ...) && sizeof...(TaskK) <= 1, "TaskK: none or ChainTaskK");
+  static_assert(CostPack<TaskK...>::value, "TaskK: none or ChainTaskK, then none or ChainGoalRows");
   static_assert(kernarg_bytes<ChainK<double, NJ>, TaskK..., int, int, ChainIter<double>, const int32_t*,
                               LSParams>() <= HIP_KERNARG_LIMIT,
                 "the chain constants by value: the argument block within HIP's limit");
@@ -2505,7 +2594,8 @@ __global__ __launch_bounds__(CH32_WG) void chain_iter_forward32_kernel(ChainK<do
   }
   double du2 = 0.0;
   const double pc = a.prev_cost ? a.prev_cost[b] : (double)INFINITY;
-  const ChainFwdOut<double> r = chain_forward_group32<NJ, NU, sizeof...(TaskK) == 1>(
+  constexpr bool TASK = pack_count<ChainTaskK, TaskK...> == 1, ROWS = pack_count<ChainGoalRows, TaskK...> == 1;
+  const ChainFwdOut<double> r = chain_forward_group32<NJ, NU, TASK, ROWS>(
       Ps, stage + (threadIdx.x / CH32_LANES) * STAGE, b, T, a.x, a.u, a.xtraj, a.d, a.K, pc, a.xnew, a.unew, &du2,
       ls, C...);
   if (l32 != 0) return;
@@ -2554,6 +2644,14 @@ struct ilqr_chain_handle {
   // composed on the device, these are the kernel argument
   ilqr::ChainTaskK taskk{};
   bool task_mode() const { return cost_mode != ILQR_CHAIN_COST_JOINT; }
+  // a goal per trajectory (ilqr_chain_set_joint_targets, _set_task_targets): the handle's
+  // copies of the rows, (batch, n_joints) and (batch, 3), allocated at the first call and
+  // kept; `on` while an override is set. Each applies while its cost family is in effect.
+  double *joint_rows = nullptr, *task_rows = nullptr;
+  bool joint_rows_on = false, task_rows_on = false;
+  const double* goal_rows() const {
+    return task_mode() ? (task_rows_on ? task_rows : nullptr) : (joint_rows_on ? joint_rows : nullptr);
+  }
 };
 
 namespace {
@@ -2955,17 +3053,27 @@ struct ChainTilesOps {
     hipError_t e = linearize(h, x, u, st, h->tA, h->tB);
     if (e != hipSuccess) return e;
     const size_t n = (size_t)h->batch * (h->T + 1) * (NX + NU);
-    ilqr::chain_cost_tiles_kernel<NJ, NU><<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(
-        cost_consts(h->chain), h->batch, h->T, x, u, st, h->lx, h->lu, h->lfx);
+    if (const double* rows = h->goal_rows(); rows && !h->task_mode())  // θ* per trajectory
+      ilqr::chain_cost_tiles_kernel<NJ, NU, ilqr::ChainGoalRows><<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(
+          cost_consts(h->chain), ilqr::ChainGoalRows{rows}, h->batch, h->T, x, u, st, h->lx, h->lu, h->lfx);
+    else
+      ilqr::chain_cost_tiles_kernel<NJ, NU><<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(
+          cost_consts(h->chain), h->batch, h->T, x, u, st, h->lx, h->lu, h->lfx);
     if ((e = hipGetLastError()) != hipSuccess || !h->task_mode()) return e;
     // a task mode: lx = 0 and lu = 2u came from the weights above; the terminal tiles from x_N
     return quadratize(h, x + (size_t)h->T * NX, (size_t)(h->T + 1) * NX, h->batch, st, nullptr, h->lfx, h->lfxx);
   }
-  // final_cost_quadratization of the cost in effect at n states x[s·stride .. +NX)
+  // final_cost_quadratization of the cost in effect at n states x[s·stride .. +NX); with a
+  // goal per trajectory of that cost, state s against row s (the callers hold n to batch)
   static hipError_t quadratize(ilqr_chain_handle* h, const V* x, size_t stride, int n, const int32_t* st, V* cost,
                                V* grad, V* hess) {
-    ilqr::chain_task_quad_kernel<NJ><<<(n + 63) / 64, 64, 0, h->stream>>>(
-        chain_consts<V, NJ>(h->chain), h->taskk, h->task_mode() ? 0 : 1, n, x, stride, st, cost, grad, hess);
+    if (const double* rows = h->goal_rows())
+      ilqr::chain_task_quad_kernel<NJ, ilqr::ChainGoalRows><<<(n + 63) / 64, 64, 0, h->stream>>>(
+          chain_consts<V, NJ>(h->chain), h->taskk, ilqr::ChainGoalRows{rows}, h->task_mode() ? 0 : 1, n, x, stride,
+          st, cost, grad, hess);
+    else
+      ilqr::chain_task_quad_kernel<NJ><<<(n + 63) / 64, 64, 0, h->stream>>>(
+          chain_consts<V, NJ>(h->chain), h->taskk, h->task_mode() ? 0 : 1, n, x, stride, st, cost, grad, hess);
     return hipGetLastError();
   }
   static ilqr::TileParams tile_params(const ilqr_chain_handle* h) {
@@ -2983,7 +3091,15 @@ struct ChainTilesOps {
                             const ilqr::LSParams& ls) {
     const auto P = chain_consts<V, NJ>(h->chain);
     const int grid = (h->batch * ilqr::CH32_LANES + ilqr::CH32_WG - 1) / ilqr::CH32_WG;
-    if (h->task_mode())
+    const ilqr::ChainGoalRows rows{h->goal_rows()};  // a goal per trajectory of the cost in effect
+    if (rows.rows && h->task_mode())
+      ilqr::chain_forward32_kernel<NJ, NU, ilqr::ChainTaskK, ilqr::ChainGoalRows>
+          <<<grid, ilqr::CH32_WG, 0, h->stream>>>(P, h->taskk, rows, h->batch, h->T, x, u, xt, d, K, pc, xn, un, nc,
+                                                  tr, st, ls);
+    else if (rows.rows)
+      ilqr::chain_forward32_kernel<NJ, NU, ilqr::ChainGoalRows><<<grid, ilqr::CH32_WG, 0, h->stream>>>(
+          P, rows, h->batch, h->T, x, u, xt, d, K, pc, xn, un, nc, tr, st, ls);
+    else if (h->task_mode())
       ilqr::chain_forward32_kernel<NJ, NU, ilqr::ChainTaskK><<<grid, ilqr::CH32_WG, 0, h->stream>>>(
           P, h->taskk, h->batch, h->T, x, u, xt, d, K, pc, xn, un, nc, tr, st, ls);
     else
@@ -3001,7 +3117,14 @@ struct ChainTilesOps {
     if (e != hipSuccess) return e;
     const auto P = chain_consts<V, NJ>(h->chain);
     const int grid = (h->batch * ilqr::CH32_LANES + ilqr::CH32_WG - 1) / ilqr::CH32_WG;
-    if (h->task_mode())
+    const ilqr::ChainGoalRows rows{h->goal_rows()};
+    if (rows.rows && h->task_mode())
+      ilqr::chain_iter_forward32_kernel<NJ, NU, ilqr::ChainTaskK, ilqr::ChainGoalRows>
+          <<<grid, ilqr::CH32_WG, 0, h->stream>>>(P, h->taskk, rows, h->batch, h->T, a, h->bstatus, ls);
+    else if (rows.rows)
+      ilqr::chain_iter_forward32_kernel<NJ, NU, ilqr::ChainGoalRows><<<grid, ilqr::CH32_WG, 0, h->stream>>>(
+          P, rows, h->batch, h->T, a, h->bstatus, ls);
+    else if (h->task_mode())
       ilqr::chain_iter_forward32_kernel<NJ, NU, ilqr::ChainTaskK><<<grid, ilqr::CH32_WG, 0, h->stream>>>(
           P, h->taskk, h->batch, h->T, a, h->bstatus, ls);
     else
@@ -3164,6 +3287,30 @@ ilqr_status chain_tiles_set_cost_mode(ilqr_chain_handle* h, int32_t mode) {
   CH_TRY(hipSetDevice(h->device));
   apply_cost_mode(h, mode);
   CH_TRY(tiles_hessians(h));
+  return ILQR_OK;
+}
+
+// ilqr_chain_set_joint_targets / _set_task_targets: (batch, width) device doubles into the
+// handle's own buffer (allocated at the first call, kept until ilqr_chain_destroy) by a
+// device-to-device copy on the handle's stream, after the launches already enqueued there
+// and waited for, so that the caller's array is free when the call returns. NULL clears the
+// override and keeps the buffer.
+ilqr_status chain_set_goal_rows(ilqr_chain_handle* h, const double* targets, size_t width, double** rows, bool* on,
+                                const char* who) {
+  if (!on_tiles(h)) {
+    g_chain_error = std::string(who) + ": needs a handle that iterates on the tiles path (4 to 7 joints, fp64)";
+    return ILQR_ERR_UNSUPPORTED;
+  }
+  if (!targets) {
+    *on = false;
+    return ILQR_OK;
+  }
+  const size_t bytes = sizeof(double) * (size_t)h->batch * width;
+  CH_TRY(hipSetDevice(h->device));
+  if (!*rows) CH_TRY(hipMalloc(rows, bytes));
+  CH_TRY(hipMemcpyAsync(*rows, targets, bytes, hipMemcpyDeviceToDevice, h->stream));
+  CH_TRY(hipStreamSynchronize(h->stream));
+  *on = true;
   return ILQR_OK;
 }
 
@@ -3337,6 +3484,7 @@ ilqr_status ilqr_chain_final_cost_quadratize(ilqr_chain_handle* h, const void* x
   if (!h || !x) return ILQR_ERR_BAD_ARG;
   if (n <= 0) return ILQR_ERR_BAD_DIMS;
   if (!on_tiles(h)) return ILQR_ERR_UNSUPPORTED;
+  if (h->goal_rows() && n != h->batch) return ILQR_ERR_BAD_DIMS;  // state s against row s
   CH_TRY(hipSetDevice(h->device));
   CH_TRY(with_tiles_ops(h, [&](auto ops) {
     using O = decltype(ops);
@@ -3346,6 +3494,21 @@ ilqr_status ilqr_chain_final_cost_quadratize(ilqr_chain_handle* h, const void* x
 }
 
 int32_t ilqr_chain_get_cost_mode(const ilqr_chain_handle* h) { return h ? h->cost_mode : -1; }
+
+ilqr_status ilqr_chain_set_joint_targets(ilqr_chain_handle* h, const double* targets) {
+  if (!h) return ILQR_ERR_BAD_ARG;
+  return chain_set_goal_rows(h, targets, (size_t)h->nj, &h->joint_rows, &h->joint_rows_on,
+                             "ilqr_chain_set_joint_targets");
+}
+
+ilqr_status ilqr_chain_set_task_targets(ilqr_chain_handle* h, const double* targets) {
+  if (!h) return ILQR_ERR_BAD_ARG;
+  return chain_set_goal_rows(h, targets, 3, &h->task_rows, &h->task_rows_on, "ilqr_chain_set_task_targets");
+}
+
+int32_t ilqr_chain_get_target_mode(const ilqr_chain_handle* h) {
+  return h ? (h->joint_rows_on ? 1 : 0) | (h->task_rows_on ? 2 : 0) : -1;
+}
 
 int32_t ilqr_chain_get_dynamics(const ilqr_chain_handle* h) {
   if (!h) return -1;
@@ -3366,6 +3529,8 @@ ilqr_status ilqr_chain_destroy(ilqr_chain_handle* h) {
   (void)hipFree(h->bstatus);
   ilqr::fit_state_destroy(&h->fit);
   (void)hipFree(h->task_dev);
+  (void)hipFree(h->joint_rows);
+  (void)hipFree(h->task_rows);
   delete h;
   return ILQR_OK;
 }

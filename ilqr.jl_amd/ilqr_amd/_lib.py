@@ -61,6 +61,8 @@ CHAIN_DYN_CLOSED_FORM = 2
 CHAIN_COST_JOINT = 0            # ilqr_chain_cost_mode (cost_functions.jl's factories)
 CHAIN_COST_SIMPLE = 1
 CHAIN_COST_SIMPLE_EUCLIDEAN = 2
+CHAIN_TARGETS_JOINT = 1         # ilqr_chain_get_target_mode's bits: goals per trajectory
+CHAIN_TARGETS_TASK = 2
 CHAIN_MAX_JOINTS = 8
 
 
@@ -168,6 +170,9 @@ SIGNATURES = {
                                             C.POINTER(C.c_double), C.c_double]),
     "ilqr_chain_final_cost_quadratize": (C.c_int, [P, P, C.c_int, P, P, P]),
     "ilqr_chain_get_cost_mode": (C.c_int32, [P]),
+    "ilqr_chain_set_joint_targets": (C.c_int, [P, P]),
+    "ilqr_chain_set_task_targets": (C.c_int, [P, P]),
+    "ilqr_chain_get_target_mode": (C.c_int32, [P]),
     "ilqr_chain_sync": (C.c_int, [P]),
     "ilqr_chain_dynamics": (C.c_int, [P, P, P, P, C.c_int]),
     "ilqr_chain_linearize": (C.c_int, [P, P, P, P, P]),

@@ -329,10 +329,40 @@ class ChainSolver:
 
     clear_simple_costs = set_joint_costs
 
+    def _set_targets(self, fn, name, targets, width):
+        if targets is not None:
+            if not isinstance(targets, torch.Tensor):   # a host array: uploaded, then copied by the call
+                targets = torch.as_tensor(np.ascontiguousarray(targets), device=self.dev)
+            _req(targets, torch.float64, (self.batch, width), "targets")
+        self._bind()   # the rows are copied on the handle's stream
+        _lib.check(fn(self.h, _ptr(targets)), name)
+
+    def set_joint_targets(self, targets):
+        """A joint-space goal θ* per trajectory (ilqr_chain_set_joint_targets; four to seven
+        joints, fp64): a float64 CUDA tensor, or a host array, of shape (batch, n_joints), row b
+        replacing the problem's `target` for trajectory b while the joint-space costs are in
+        effect. The handle keeps a copy (the caller's tensor is free when this returns); a
+        further call replaces the rows without allocating; None restores the problem's target."""
+        self._set_targets(self.lib.ilqr_chain_set_joint_targets, "ilqr_chain_set_joint_targets", targets, self.nj)
+
+    def set_task_targets(self, targets):
+        """A task-space goal per trajectory (ilqr_chain_set_task_targets): shape (batch, 3), row
+        b replacing set_simple_costs' final_target for trajectory b in either task reading;
+        None restores it. Copy semantics as set_joint_targets."""
+        self._set_targets(self.lib.ilqr_chain_set_task_targets, "ilqr_chain_set_task_targets", targets, 3)
+
+    @property
+    def target_mode(self) -> frozenset:
+        """Which goals are per trajectory: a subset of {"joint", "task"}."""
+        m = int(self.lib.ilqr_chain_get_target_mode(self.h))
+        return frozenset(k for k, bit in (("joint", _lib.CHAIN_TARGETS_JOINT), ("task", _lib.CHAIN_TARGETS_TASK))
+                         if m & bit)
+
     def final_cost_quadratization(self, x):
         """final_cost_quadratization (backward_pass.jl:134-153) of the cost in effect at the
         states x (n, nx): (ℓ_f (n,), ∇ℓ_f (n, nx), ∇²ℓ_f (n, nx, nx)) on the device
-        (ilqr_chain_final_cost_quadratize: four to seven joints, fp64)."""
+        (ilqr_chain_final_cost_quadratize: four to seven joints, fp64). With goals per
+        trajectory of the mode in effect, state s is paired with goal s and n must be batch."""
         n = x.shape[0]
         _req(x, torch.float64, (n, self.nx), "x")
         cost = self._new(n, dtype=torch.float64)

@@ -871,6 +871,7 @@ mutable struct ChainSolver
     h::Handle                # device-memory helper (ilqr_malloc / memcpy), closed with it
     x::Ptr{Cvoid}; u::Ptr{Cvoid}; xo::Ptr{Cvoid}; uo::Ptr{Cvoid}; status::Ptr{Int32}
     lock::ReentrantLock
+    nj::Int; nb::Int         # joints and batch: the shape of a goal per trajectory
 end
 
 function ChainSolver(c::Chain, nx::Integer, nu::Integer, T::Integer, nb::Integer, ::Type{E}, linearization,
@@ -906,7 +907,7 @@ function ChainSolver(c::Chain, nx::Integer, nu::Integer, T::Integer, nb::Integer
     h = Handle(nx, nu, T, 1; device=device)  # device-memory helper only
     a(n) = Ptr{Cvoid}(alloc(h, E, n))
     s = ChainSolver(r[], h, a(nb * (T + 1) * nx), a(nb * T * nu), a(nb * (T + 1) * nx), a(nb * T * nu),
-                    alloc(h, Int32, nb), ReentrantLock())
+                    alloc(h, Int32, nb), ReentrantLock(), Int(c.n_joints), Int(nb))
     finalizer(destroy!, s)      # a backstop; close(s) frees everything at once
     return s
 end
@@ -917,6 +918,42 @@ function destroy!(s::ChainSolver)
     return nothing
 end
 Base.close(s::ChainSolver) = lock(() -> destroy!(s), s.lock)
+
+# A goal per trajectory (ilqr_chain_set_joint_targets / ilqr_chain_set_task_targets; 4 to 7
+# joints in fp64): a Julia (n_joints, batch) or (3, batch) column-major Matrix{Float64} is the
+# same bytes as the C ABI's row-major (batch, n_joints) / (batch, 3), so it goes up as it is.
+# The handle copies the rows before the call returns; `nothing` clears the override.
+function set_targets!(set, s::ChainSolver, what::String, targets::Union{Nothing,Matrix{Float64}}, rows::Integer)
+    if targets === nothing
+        check(set(Ptr{Float64}(C_NULL)), what)
+        return s
+    end
+    size(targets) == (rows, s.nb) || throw(DimensionMismatch("$what: expected ($rows, $(s.nb)), got $(size(targets))"))
+    p = upload(s.h, targets)
+    try
+        check(set(p), what)
+    finally
+        release!(s.h, p)
+    end
+    return s
+end
+
+"""set_joint_targets!(s, targets): θ* per trajectory, `targets` (n_joints, batch), column b the
+goal of trajectory b while the joint-space costs are in effect; `nothing` restores the chain's
+target."""
+set_joint_targets!(s::ChainSolver, targets::Union{Nothing,Matrix{Float64}}) =
+    set_targets!(s, "ilqr_chain_set_joint_targets", targets, s.nj) do p
+        ccall((:ilqr_chain_set_joint_targets, libilqr), Cint, (Ptr{Cvoid}, Ptr{Float64}), s.ch, p)
+    end
+
+"""set_task_targets!(s, targets): final_target per trajectory, `targets` (3, batch), in either
+task reading of simple_costs; `nothing` restores the costs' own final_target."""
+set_task_targets!(s::ChainSolver, targets::Union{Nothing,Matrix{Float64}}) =
+    set_targets!(s, "ilqr_chain_set_task_targets", targets, 3) do p
+        ccall((:ilqr_chain_set_task_targets, libilqr), Cint, (Ptr{Cvoid}, Ptr{Float64}), s.ch, p)
+    end
+
+target_mode(s::ChainSolver) = ccall((:ilqr_chain_get_target_mode, libilqr), Int32, (Ptr{Cvoid},), s.ch)
 
 const CHAIN_CACHE = Dict{Tuple{Chain,Int,Int,DataType,Int32,Int32,Union{Nothing,SimpleCosts}},ChainSolver}()
 
@@ -932,7 +969,9 @@ about twelve times faster to form at six joints; ilqr_chain_create refuses it el
 2-joint evaluator (AUTO: the closed form sampled from the Newton-Euler recursion at
 creation; RNEA: the recursion itself). `costs = simple_costs(…)` replaces the chain's
 joint-space costs with cost_functions.jl's pair (2-joint chains: the closed form,
-ilqr_chain_set_simple_costs; 4 to 7 joints in fp64: ilqr_chain_set_task_costs). Nothing here
+ilqr_chain_set_simple_costs; 4 to 7 joints in fp64: ilqr_chain_set_task_costs).
+`joint_targets` (n_joints, batch) / `task_targets` (3, batch) give every trajectory a goal of its
+own (4 to 7 joints in fp64: set_joint_targets!, set_task_targets!), for this call. Nothing here
 depends on the joint count: a chain of n_joints = nu = 4, 5, 6 or 7 (the 6-DoF arm, a 7-DoF
 manipulator) iterates in fp64 (ilqr_chain_supported_dtype(n, n, ILQR_F64) == 1), so it takes
 Array{Float64,3}; with
@@ -942,12 +981,18 @@ chain_fit allocates nothing per call (clear_cache!() closes them)."""
 function chain_fit(c::Chain, x_init::Array{E,3}, u_init::Array{E,3}; max_iter::Int64=100,
                    tol::Float64=1e-6, linearization=ILQR_LINEARIZE_DUAL,
                    dynamics=ILQR_CHAIN_DYN_AUTO,
-                   costs::Union{Nothing,SimpleCosts}=nothing) where {E<:Union{Float32,Float64}}
+                   costs::Union{Nothing,SimpleCosts}=nothing,
+                   joint_targets::Union{Nothing,Matrix{Float64}}=nothing,
+                   task_targets::Union{Nothing,Matrix{Float64}}=nothing) where {E<:Union{Float32,Float64}}
     nx, N, nb = size(x_init); nu = size(u_init, 1); M = N - 1
     @assert(size(u_init, 2) == M)
     key = (c, M, nb, E, Int32(linearization), Int32(dynamics), costs)
     return with_cached(CHAIN_CACHE, () -> ChainSolver(c, nx, nu, M, nb, E, linearization, dynamics, costs), key) do s
         upload!(s.h, s.x, x_init); upload!(s.h, s.u, u_init)
+        # the cached handle keeps an override until it is cleared: this call's goals, or none
+        m = target_mode(s)
+        (joint_targets !== nothing || m & 1 != 0) && set_joint_targets!(s, joint_targets)
+        (task_targets !== nothing || m & 2 != 0) && set_task_targets!(s, task_targets)
         o = default_options(); o.max_iter = max_iter; o.tol = tol
         st = ccall((:ilqr_chain_fit, libilqr), Cint,
                    (Ptr{Cvoid}, Ref{Options}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},

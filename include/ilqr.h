@@ -323,7 +323,10 @@ ilqr_status ilqr_fit_ex(ilqr_handle* h, const ilqr_problem* p, const ilqr_option
  * Newton-Euler only: ilqr_chain_set_simple_costs and ilqr_chain_set_dynamics(CLOSED_FORM)
  * return ILQR_ERR_UNSUPPORTED, AUTO and RNEA both mean the recursion. Their task-space
  * costs of cost_functions.jl are ilqr_chain_set_task_costs (kinematics composed on the
- * device, fp64).
+ * device, fp64). The trajectories of such a handle are independent problems, not only
+ * independent starts: ilqr_chain_set_joint_targets / ilqr_chain_set_task_targets give every
+ * trajectory its own θ* or final_target (one `target` / final_target for the whole batch
+ * otherwise), as every fit call of the reference has its own closures.
  * Device memory taken at creation, per (trajectory, step): a 2-joint handle keeps one
  * linearisation record (nx(nx + nu) + nx + nu words), an fp64 handle of 4 to 7 joints the
  * tiles of the Riccati tiles kernel instead — A nx², B nx·nu, lxx nx², luu nu², lx nx, lu nu
@@ -447,6 +450,38 @@ ilqr_status ilqr_chain_final_cost_quadratize(ilqr_chain_handle* h, const void* x
                                              void* cost, void* grad, void* hess);
 /* the cost mode in effect, −1 for a NULL handle */
 int32_t ilqr_chain_get_cost_mode(const ilqr_chain_handle* h);
+/* A goal per trajectory, for handles that iterate on the tiles path (4 to 7 joints, fp64):
+ * in the reference every fit call has its own closures and hence its own target_pose /
+ * final_target; here row b of `targets` is trajectory b's.
+ *   ilqr_chain_set_joint_targets: (batch, n_joints) device doubles; row b replaces
+ *     ilqr_chain.target (θ*) in immediate_cost, final_cost and their quadratizations for
+ *     trajectory b while the cost mode is ILQR_CHAIN_COST_JOINT (the forward's error stays
+ *     θ*_b − (x̄ − x_traj)); NULL restores ilqr_chain.target for every trajectory.
+ *   ilqr_chain_set_task_targets: (batch, 3) device doubles; row b replaces
+ *     ilqr_chain_set_task_costs' final_target in ℓ_f and its quadratization for trajectory b
+ *     in either task mode (ILQR_CHAIN_COST_SIMPLE keeps its "p_z against every component"
+ *     reading, against row b); NULL restores that final_target.
+ * The rows are copied into a buffer the handle owns (allocated at the first call of each
+ * setter, reused afterwards) by a device-to-device copy on the handle's stream: the caller
+ * may overwrite or free its array when the call returns, and a further call replaces the
+ * rows without allocating (new goals before every fit). An override stays until it is
+ * cleared with NULL and applies whenever its cost family is in effect:
+ * ilqr_chain_set_task_costs switching the mode neither drops nor applies the other
+ * family's rows. Weights, body and point stay the handle's. backward, forward, iterate,
+ * fit and fit_ex honour the rows with every linearisation and with x_traj;
+ * ilqr_chain_final_cost_quadratize, with rows of the mode in effect, pairs state s with
+ * row s and then requires n == batch (ILQR_ERR_BAD_DIMS otherwise). A handle without rows
+ * launches the kernels it launched before these entry points existed.
+ * The rows are NOT validated (they live on the device): a NaN in row b ends trajectory b
+ * alone, through ILQR_TRAJ_NAN, like a NaN in its x or u.
+ * Returns: NULL handle → ILQR_ERR_BAD_ARG before any device call; a handle that does not
+ * iterate on the tiles path (any 2-joint chain, 4 to 7 joints in ILQR_F32) →
+ * ILQR_ERR_UNSUPPORTED with a sentence in ilqr_chain_last_error. */
+ilqr_status ilqr_chain_set_joint_targets(ilqr_chain_handle* h, const double* targets);
+ilqr_status ilqr_chain_set_task_targets(ilqr_chain_handle* h, const double* targets);
+/* bit 0: joint targets per trajectory, bit 1: task targets per trajectory; −1 for a NULL
+ * handle */
+int32_t ilqr_chain_get_target_mode(const ilqr_chain_handle* h);
 ilqr_status ilqr_chain_sync(ilqr_chain_handle* h);
 /* dynamicsf for n independent (x, u) pairs: x (n, nx), u (n, nu) → x_next (n, nx) */
 ilqr_status ilqr_chain_dynamics(ilqr_chain_handle* h, const void* x, const void* u, void* x_next,

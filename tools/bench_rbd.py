@@ -31,6 +31,9 @@ from tools import flops as FL  # noqa: E402
 
 # --simple-cost: the task cost of tests/golden/chain6task_euc_t30 (six joints)
 SIMPLE_COST = {"point": [0.05, 0.02, 0.1], "final_target": [3.9, 3.5, 1.3], "weight": 2e3}
+# --targets per-trajectory: trajectory b's goal is the problem's plus U(-TARGET_SPREAD, TARGET_SPREAD)
+# per component from numpy.random.default_rng(TARGET_SEED + b)
+TARGET_SEED, TARGET_SPREAD = 1000, 0.3
 PEAK_TFLOPS = {"f32": 157.3, "f64": 78.6}   # MI355X vector FP32 / FP64 (spec; MI355X_MICROARCH.md)
 
 
@@ -69,10 +72,12 @@ def cpu_baseline(pr, x, u, budget_s):
 
 def measure(lin="fd", B=2048, T=100, nu=1, dtype="f32", steps=100, warmup=100, device=0,
             dynamics="auto", cpu_budget=None, base=None, problem=None, simple_cost=False, robot=None,
-            fit=True):
+            fit=True, targets="shared"):
     """Config 5's fit-iteration rate and per-kernel roofline for one linearisation (one
     dict; bench.py's secondary_configs calls this after its headline, outside the
-    headline's timed region)."""
+    headline's timed region). targets="per-trajectory" (4 to 7 joints): every trajectory
+    its own goal, the problem's plus an offset from default_rng(TARGET_SEED + b)
+    (ilqr_chain_set_joint_targets, or _set_task_targets with simple_cost)."""
     dt = torch.float32 if dtype == "f32" else torch.float64
     dev = torch.device("cuda", device)
     # problem: another chain (the coupled 2-joint test chain: q-dependent M and bias, which
@@ -84,6 +89,11 @@ def measure(lin="fd", B=2048, T=100, nu=1, dtype="f32", steps=100, warmup=100, d
     if simple_cost:  # cost_functions.jl's pair: the tool point's squared distance to a reachable target
         s.set_simple_costs(pr.n_joints - 1, SIMPLE_COST["point"], SIMPLE_COST["final_target"],
                            SIMPLE_COST["weight"], euclidean=True)
+    if targets == "per-trajectory":
+        goal = np.array(SIMPLE_COST["final_target"]) if simple_cost else pr.target
+        rows = np.stack([goal + np.random.default_rng(TARGET_SEED + b).uniform(-TARGET_SPREAD, TARGET_SPREAD,
+                                                                               goal.size) for b in range(B)])
+        (s.set_task_targets if simple_cost else s.set_joint_targets)(rows)
     u = torch.zeros((B, T, pr.nu), dtype=dt, device=dev)
     x = s.rollout(torch.from_numpy(x0).to(dev, dt), u)
     xn, un = torch.empty_like(x), torch.empty_like(u)
@@ -168,7 +178,7 @@ def measure(lin="fd", B=2048, T=100, nu=1, dtype="f32", steps=100, warmup=100, d
                                    f"gravity {[float(v) for v in pr.chain.gravity]})" if tiles else
                                    "BASELINE config 5 (RBD_2_link_example, fixed base)"),
                       "batch": B, "T": T, "linearization": lin, "dynamics": s.dynamics_mode,
-                      "cost_mode": s.cost_mode,
+                      "cost_mode": s.cost_mode, "targets": targets,
                       "closed_form_check": s.closed_form_error},
            "traj_iters_per_s": B * 1000.0 / ms,
            "mean_line_search_trials": float(trials.double().mean().item()), "all_ok": ok,
@@ -234,6 +244,9 @@ def main():
     ap.add_argument("--simple-cost", action="store_true",
                     help="6dof_arm, coupled: cost_functions.jl's task-space costs (ilqr_chain_set_task_costs) in place "
                          "of the joint-space ones; no CPU baseline (the C restatement has the joint costs)")
+    ap.add_argument("--targets", default="shared", choices=["shared", "per-trajectory"],
+                    help="per-trajectory (6dof_arm, coupled): a goal per trajectory, the problem's plus a seeded "
+                         "per-trajectory offset (ilqr_chain_set_joint_targets / _set_task_targets)")
     ap.add_argument("--no-fit", action="store_true",
                     help="skip the end-to-end ChainSolver.fit timing (90 synchronous fits)")
     args = ap.parse_args()
@@ -253,13 +266,15 @@ def main():
         robot = f"coupled_chain_problem({args.joints})"
     if args.simple_cost and args.robot == "2dof_arm":
         ap.error("--simple-cost goes with --robot 6dof_arm or coupled")
+    if args.targets != "shared" and args.robot == "2dof_arm":
+        ap.error("--targets per-trajectory goes with --robot 6dof_arm or coupled (the tiles path)")
     for lin in args.lin.split(","):
         res = measure(lin, args.batch, args.T, args.nu, args.dtype, args.steps, args.warmup,
                       dynamics=args.dynamics,
                       cpu_budget=None if args.no_cpu or args.simple_cost or lin == "analytic" else args.cpu_budget,
                       base=base,
                       problem=problem, simple_cost=args.simple_cost, robot=robot,
-                      fit=not args.no_fit)
+                      fit=not args.no_fit, targets=args.targets)
         base = res["cpu_baseline"] or base
         print(json.dumps(res), flush=True)
 
