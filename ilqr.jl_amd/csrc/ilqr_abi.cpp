@@ -70,6 +70,20 @@ struct ilqr_handle {
   // the allocation failed): every iteration runs the full recursion
   bool full_bw = false;
   double* fac = nullptr;
+  // ... and across fit calls: K and fac stay valid for the next fit as long as the operands
+  // they were computed from (IterArgs::snap, the storing wave's snapshot) and μ are the
+  // same bits. The next fit's first iteration checks that on the device, wave by wave
+  // (lq_iter_fused4_check_kernel), and re-factors only where it fails.
+  // ILQR_SCHED_REUSE_PER_CALL turns it off; snap == nullptr (the allocation failed): off.
+  bool per_call = false;
+  double* snap = nullptr;
+  int32_t* branch = nullptr;  // per wave of the last fit's first iteration: 1 reused, 0 re-factored
+  bool branch_set = false;    // the last fit wrote `branch` (ilqr_reuse_record)
+  // K, fac and snap are those of a fit on the fused reuse path that returned without a HIP
+  // error, at μ = reuse_mu; cleared on entry of everything else that writes K or fac
+  bool reuse_valid = false;
+  double reuse_mu = 0.0;
+  bool check_now = false;  // ilqr_fit_ex → enqueue_iteration: this fit's first launch checks
   ilqr::LSCoopRec* coop_rec = nullptr;
   double* coop_cost = nullptr;
   double* coop_du2 = nullptr;
@@ -201,7 +215,10 @@ ilqr_status enqueue_iteration(ilqr_handle* h, const ilqr_problem* p, const ilqr:
       ac.coop_gen = coop ? ++h->coop_gen : h->coop_gen;
       // fit's iterations ≥ 2 reuse the gains and the factor its first one stored
       const bool vec = a.fac && a.iter >= 2;
-      HIP_TRY(ilqr::launch_lq_iter_fused4(P, h->batch, h->T, ac, ls, h->stream, h->fw_mfma, vec));
+      // its first one checks the handle's stored gains against the problem instead, if
+      // ilqr_fit_ex found them valid
+      const bool check = !vec && a.init && a.fac && a.snap && h->check_now;
+      HIP_TRY(ilqr::launch_lq_iter_fused4(P, h->batch, h->T, ac, ls, h->stream, h->fw_mfma, vec, check));
       return ILQR_OK;
     }
     HIP_TRY(ilqr::launch_lq_iter_backward(h->nx, h->nu, P, 0, h->batch, h->T, a, ls.mu, h->stream, h->bw_wave));
@@ -267,6 +284,7 @@ ilqr_status ensure_pad(ilqr_handle* h) {
   h->pad->bw_wave = h->bw_wave;
   h->pad->coop = h->coop;
   h->pad->full_bw = h->full_bw;
+  h->pad->per_call = h->per_call;
   return ILQR_OK;
 }
 
@@ -448,6 +466,17 @@ ilqr_status ilqr_create(ilqr_handle** out, int device, int nx, int nu, int T, in
       (void)hipGetLastError();
       h->fac = nullptr;
     }
+    // the operand snapshot of those gains (31 doubles per lane: the size of the problem
+    // itself, 16 MB at B = 4096) and the per-wave branch record; without them reuse stays
+    // within one call
+    if (e == hipSuccess && h->fac &&
+        (hipMalloc(&h->snap, sizeof(double) * ilqr::lq_snap_doubles(B)) != hipSuccess ||
+         hipMalloc(&h->branch, sizeof(int32_t) * ilqr::lq_fused_waves(B)) != hipSuccess)) {
+      (void)hipGetLastError();
+      (void)hipFree(h->snap);
+      h->snap = nullptr;
+      h->branch = nullptr;
+    }
     if (e == hipSuccess) e = hipDeviceSynchronize();
   }
   if (e == hipSuccess && ilqr::tl_supported(nx, nu))
@@ -498,6 +527,8 @@ ilqr_status ilqr_destroy(ilqr_handle* h) {
   (void)hipFree(h->coop_ctl);
   (void)hipFree(h->coop_dev);
   (void)hipFree(h->fac);
+  (void)hipFree(h->snap);
+  (void)hipFree(h->branch);
   if (h->pad) {
     (void)ilqr_destroy(h->pad);
     for (double* q : {h->pA, h->pB, h->pQ, h->pR, h->pQf, h->px, h->pu, h->pxt, h->pxn, h->pun, h->pd, h->pK})
@@ -522,7 +553,8 @@ ilqr_status ilqr_set_stream(ilqr_handle* h, void* s) {
 ilqr_status ilqr_set_schedule(ilqr_handle* h, int flags) {
   if (!h || (flags & ~(ILQR_SCHED_PIPELINED | ILQR_SCHED_RING_FORWARD | ILQR_SCHED_BACKWARD_WAVE |
                       ILQR_SCHED_BACKWARD_BLOCK | ILQR_SCHED_FUSED | ILQR_SCHED_FORWARD_MFMA |
-                      ILQR_SCHED_SEQUENTIAL_SEARCH | ILQR_SCHED_FULL_BACKWARD)) != 0)
+                      ILQR_SCHED_SEQUENTIAL_SEARCH | ILQR_SCHED_FULL_BACKWARD |
+                      ILQR_SCHED_REUSE_PER_CALL)) != 0)
     return ILQR_ERR_BAD_ARG;
   // every combination check before any handle state changes
   if ((flags & ILQR_SCHED_FUSED) && (flags & (ILQR_SCHED_BACKWARD_WAVE | ILQR_SCHED_PIPELINED)))
@@ -537,6 +569,7 @@ ilqr_status ilqr_set_schedule(ilqr_handle* h, int flags) {
     t->fw_mfma = (flags & ILQR_SCHED_FORWARD_MFMA) != 0;
     t->coop = (flags & ILQR_SCHED_SEQUENTIAL_SEARCH) == 0;
     t->full_bw = (flags & ILQR_SCHED_FULL_BACKWARD) != 0;
+    t->per_call = (flags & ILQR_SCHED_REUSE_PER_CALL) != 0;
     t->bw_wave = (flags & (ILQR_SCHED_BACKWARD_WAVE | ILQR_SCHED_PIPELINED)) != 0 ||
                  (!(flags & ILQR_SCHED_BACKWARD_BLOCK) && h->batch < BW4_MIN_BATCH);
   }
@@ -675,6 +708,7 @@ ilqr_status ilqr_iterate(ilqr_handle* h, const ilqr_problem* p, const ilqr_optio
     ILQR_TRY(unpad_x(h, h->pxn, x_new));
     return unpad_u(h, h->pun, u_new);
   }
+  h->reuse_valid = false;  // writes h->K: a fit's stored gains are gone
   ilqr::IterArgs a{};
   a.x = x;
   a.u = u;
@@ -739,6 +773,21 @@ ilqr_status ilqr_fit_ex(ilqr_handle* h, const ilqr_problem* p, const ilqr_option
   // LQ path, else by fit_begin's launch
   const bool init_in_iter = fused_path(h, p) && !pipe && o->max_iter > 0;
   const ilqr::LSParams ls = ilqr::ls_params(o);
+  // Gain reuse. Within the call (reuse_fit): iteration 1 stores the gains and the factor,
+  // iterations ≥ 2 read them back (enqueue_iteration). Across calls (keep): they stay
+  // valid for the next fit, whose iteration 1 then checks (check_now) on the device that
+  // the operands are still the snapshot's, bit for bit — the caller may rewrite the problem
+  // in place or hand over other buffers, so it is checked, never assumed. Valid means: left
+  // by a fit on this path that returned without a HIP error, at this μ; every other writer
+  // of K or fac clears it on entry, and so does this fit until it has returned. A fit
+  // with max_iter = 0 launches no iteration and changes nothing.
+  const bool reuse_fit = init_in_iter && !h->full_bw && h->fac;
+  const bool keep = reuse_fit && !h->per_call && h->snap;
+  if (o->max_iter > 0) {
+    h->check_now = keep && h->reuse_valid && std::memcmp(&h->reuse_mu, &ls.mu, sizeof(double)) == 0;
+    h->reuse_valid = false;
+    h->branch_set = reuse_fit && h->branch;
+  }
   ilqr::FitCall c;
   c.B = h->batch, c.T = h->T, c.nx = h->nx, c.nu = h->nu;
   c.max_iter = o->max_iter;
@@ -765,10 +814,10 @@ ilqr_status ilqr_fit_ex(ilqr_handle* h, const ilqr_problem* p, const ilqr_option
     a.parity = b.parity;
     a.iter = it;
     a.init = init_in_iter && it == 1;
-    // gain reuse, decided per call: iteration 1 runs the full recursion and stores the
-    // factor, iterations ≥ 2 read it and K back (enqueue_iteration). Nothing
-    // about them outlives the call: the caller may rewrite the problem in place.
-    a.fac = init_in_iter && !h->full_bw ? h->fac : nullptr;
+    // gain reuse (above): without `keep` no snapshot is written and nothing outlives the call
+    a.fac = reuse_fit ? h->fac : nullptr;
+    a.snap = keep ? h->snap : nullptr;
+    a.branch = reuse_fit && it == 1 ? h->branch : nullptr;
     return a;
   };
   if (pipe) {
@@ -804,7 +853,27 @@ ilqr_status ilqr_fit_ex(ilqr_handle* h, const ilqr_problem* p, const ilqr_option
   }
   ILQR_TRY(join(h, p));
   HIP_TRY(ilqr::fit_end(f, c, cost, iters, status, s, &st));
+  if (keep) {  // every kernel of the fit has completed without a HIP error
+    h->reuse_valid = true;
+    h->reuse_mu = ls.mu;
+  }
   return st;
+}
+
+ilqr_status ilqr_reuse_record(ilqr_handle* h, int32_t* out, int32_t capacity, int32_t* count) {
+  if (!h || !count || capacity < 0 || (capacity > 0 && !out)) return ILQR_ERR_BAD_ARG;
+  if (h->pad && lq_paddable(h->nx, h->nu)) h = h->pad;  // a padded shape fits on its inner handle
+  *count = 0;
+  if (!h->branch_set) return ILQR_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  const int32_t n = (int32_t)ilqr::lq_fused_waves((size_t)h->batch);
+  const int32_t m = std::min(n, capacity);
+  if (m > 0) {
+    HIP_TRY(hipMemcpyAsync(out, h->branch, sizeof(int32_t) * m, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  }
+  *count = n;
+  return ILQR_OK;
 }
 
 ilqr_status ilqr_malloc(ilqr_handle* h, size_t bytes, void** ptr) {

@@ -111,16 +111,120 @@ __device__ __forceinline__ void buf_st(double v, __amdgpu_buffer_rsrc_t r, uint3
 //              select, a product and an exact MFMA transpose, off the s chain), and the
 //              same source lines then run on the same operands. Writes d only. Its
 //              inputs are prefetched BW4_PF steps ahead in registers.
-enum { BW4_FULL = 0, BW4_STORE = 1, BW4_VEC = 2 };
+//  * BW4_CHECK the first iteration of a fit on a handle that holds an earlier fit's gains
+//              (reuse across calls): the wave compares the operands of the matrix side
+//              (BW4Ops, below) with the snapshot the storing wave left, bit for bit, and
+//              runs BW4_VEC if every lane's are the same, else BW4_STORE.
+enum { BW4_FULL = 0, BW4_STORE = 1, BW4_VEC = 2, BW4_CHECK = 3 };
 constexpr int BW4_PF = 8;  // with the x/u loads and the d stores: < 64 operations in flight (vmcnt)
+
+// What the matrix side of the recursion reads besides μ and T, as the prologue leaves it in
+// each lane: the blocks of F = [A | B], of L = Q + Qᵀ, R + Rᵀ and the terminal S = Qf + Qfᵀ.
+// The same operands give the same gains and factor, bit for bit: the argument the reuse
+// within a call rests on, carried across calls by the snapshot of exactly these values
+// (BW4_SNAP doubles per lane; per wave element i of lane l at [i·64 + l], so a wave's loads
+// and stores of one element are one 512-byte line). Lanes of slots past B hold trajectory
+// B − 1's and are stored and compared like any other.
+struct BW4Ops {
+  double F[3][4], L[3][3], LR, S[3][3];
+};
+constexpr int BW4_SNAP = 31;
+static_assert(sizeof(BW4Ops) == BW4_SNAP * sizeof(double), "the snapshot is the operand set");
+
+template <typename FN>
+__device__ __forceinline__ void bw4_ops_each(BW4Ops& o, FN&& fn) {
+  int i = 0;
+#pragma unroll
+  for (int K = 0; K < 3; ++K)
+#pragma unroll
+    for (int J = 0; J < 4; ++J) fn(o.F[K][J], i++);
+#pragma unroll
+  for (int K = 0; K < 3; ++K)
+#pragma unroll
+    for (int I = 0; I < 3; ++I) fn(o.L[K][I], i++);
+  fn(o.LR, i++);
+#pragma unroll
+  for (int K = 0; K < 3; ++K)
+#pragma unroll
+    for (int I = 0; I < 3; ++I) fn(o.S[K][I], i++);
+}
+
+template <int MODE>
+__device__ __forceinline__ unsigned lq_backward4_body(const BW4Ops& op, int b0, int B, unsigned active, int T,
+                                                      const double* __restrict__ x,
+                                                      const double* __restrict__ u,
+                                                      double* __restrict__ d_out, double* __restrict__ K_out,
+                                                      double* __restrict__ fac, double mu, double* lds);
+
+// `snap`: the handle's operand snapshots (BW4_STORE writes the wave's, BW4_CHECK compares
+// and, where it differs, rewrites it; nullptr: none kept). `rec`: per wave, 1 if the wave
+// reused the stored gains in this launch, 0 if it ran the full recursion (one store per
+// wave; nullptr: not recorded).
 template <int MODE>
 __device__ unsigned lq_backward4_wave(const LQParams& P, int b0, int B, unsigned active, int T,
                                       const double* __restrict__ x, const double* __restrict__ u,
                                       double* __restrict__ d_out, double* __restrict__ K_out,
-                                      double* __restrict__ fac, double mu, double* lds) {
-  constexpr bool VEC = MODE == BW4_VEC, STORE = MODE == BW4_STORE;
+                                      double* __restrict__ fac, double mu, double* lds,
+                                      double* __restrict__ snap = nullptr, int32_t* __restrict__ rec = nullptr) {
   constexpr int NX = 12, NU = 4;
   b0 = __builtin_amdgcn_readfirstlane(b0);
+  const int l = threadIdx.x & 63;
+  const int rho = l >> 4;
+  const int beta = (l >> 2) & 3;
+  const int kap = l & 3;
+  const int b = b0 + beta;
+  const int bc = b < B ? b : B - 1;  // clamped: every load stays in bounds
+
+  const double* Ab = P.A + (size_t)bc * NX * NX;
+  const double* Bb = P.B + (size_t)bc * NX * NU;
+  const double* Qb = P.Q + (size_t)bc * NX * NX;
+  const double* Rb = P.R + (size_t)bc * NU * NU;
+  const double* Qfb = P.Qf + (size_t)bc * NX * NX;
+
+  // F = [A | B] blocks, L = Q + Qᵀ blocks (immediate_cost_quadratization :101-106), the
+  // terminal value function's S = Qf + Qfᵀ (final_cost_quadratization :134-153)
+  BW4Ops op;
+#pragma unroll
+  for (int K = 0; K < 3; ++K) {
+    const int r = 4 * K + rho;
+#pragma unroll
+    for (int J = 0; J < 3; ++J) op.F[K][J] = Ab[r * NX + 4 * J + kap];
+    op.F[K][3] = Bb[r * NU + kap];
+#pragma unroll
+    for (int I = 0; I < 3; ++I) op.L[K][I] = Qb[r * NX + 4 * I + kap] + Qb[(4 * I + kap) * NX + r];
+#pragma unroll
+    for (int I = 0; I < 3; ++I) op.S[K][I] = Qfb[r * NX + 4 * I + kap] + Qfb[(4 * I + kap) * NX + r];
+  }
+  op.LR = Rb[rho * NU + kap] + Rb[kap * NU + rho];
+
+  if constexpr (MODE == BW4_STORE || MODE == BW4_CHECK) {
+    unsigned long long* sw =
+        snap ? reinterpret_cast<unsigned long long*>(snap) + (size_t)(b0 / BW4_SLOTS) * BW4_SNAP * 64 + l : nullptr;
+    bool same = false;
+    if constexpr (MODE == BW4_CHECK) {
+      // as 64-bit integers: −0.0 is not +0.0 (other result bits), a NaN equals itself
+      unsigned long long diff = 0;
+      if (sw)
+        bw4_ops_each(op, [&](double& v, int i) { diff |= __builtin_bit_cast(unsigned long long, v) ^ sw[i * 64]; });
+      same = sw && __ballot(diff != 0) == 0;  // wave-uniform
+    }
+    if (rec && l == 0) rec[b0 / BW4_SLOTS] = same ? 1 : 0;
+    if (same) return lq_backward4_body<BW4_VEC>(op, b0, B, active, T, x, u, d_out, K_out, fac, mu, lds);
+    if (sw) bw4_ops_each(op, [&](double& v, int i) { sw[i * 64] = __builtin_bit_cast(unsigned long long, v); });
+    return lq_backward4_body<BW4_STORE>(op, b0, B, active, T, x, u, d_out, K_out, fac, mu, lds);
+  } else {
+    return lq_backward4_body<MODE>(op, b0, B, active, T, x, u, d_out, K_out, fac, mu, lds);
+  }
+}
+
+template <int MODE>
+__device__ __forceinline__ unsigned lq_backward4_body(const BW4Ops& op, int b0, int B, unsigned active, int T,
+                                                      const double* __restrict__ x,
+                                                      const double* __restrict__ u,
+                                                      double* __restrict__ d_out, double* __restrict__ K_out,
+                                                      double* __restrict__ fac, double mu, double* lds) {
+  constexpr bool VEC = MODE == BW4_VEC, STORE = MODE == BW4_STORE;
+  constexpr int NX = 12, NU = 4;
   const int l = threadIdx.x & 63;
   const int rho = l >> 4;
   const int beta = (l >> 2) & 3;
@@ -130,24 +234,9 @@ __device__ unsigned lq_backward4_wave(const LQParams& P, int b0, int B, unsigned
   const int bc = b < B ? b : B - 1;  // clamped: every load stays in bounds
   const int nslot = B - b0 < 4 ? B - b0 : 4;
 
-  const double* Ab = P.A + (size_t)bc * NX * NX;
-  const double* Bb = P.B + (size_t)bc * NX * NU;
-  const double* Qb = P.Q + (size_t)bc * NX * NX;
-  const double* Rb = P.R + (size_t)bc * NU * NU;
-  const double* Qfb = P.Qf + (size_t)bc * NX * NX;
-
-  // F = [A | B] blocks, L = Q + Qᵀ blocks (immediate_cost_quadratization :101-106)
-  double F[3][4], L[3][3];
-#pragma unroll
-  for (int K = 0; K < 3; ++K) {
-    const int r = 4 * K + rho;
-#pragma unroll
-    for (int J = 0; J < 3; ++J) F[K][J] = Ab[r * NX + 4 * J + kap];
-    F[K][3] = Bb[r * NU + kap];
-#pragma unroll
-    for (int I = 0; I < 3; ++I) L[K][I] = Qb[r * NX + 4 * I + kap] + Qb[(4 * I + kap) * NX + r];
-  }
-  const double LR = Rb[rho * NU + kap] + Rb[kap * NU + rho];
+  const double(&F)[3][4] = op.F;
+  const double(&L)[3][3] = op.L;
+  const double LR = op.LR;
   const double LRmu = rho == kap ? LR + mu : LR;  // R + Rᵀ + μI
 
   // the block transpose within each slot on the MFMA: mf4(a, I, 0) = aᵀ, exact (products
@@ -173,10 +262,9 @@ __device__ unsigned lq_backward4_wave(const LQParams& P, int b0, int B, unsigned
     double xr[3];
 #pragma unroll
     for (int K = 0; K < 3; ++K) {
-      const int r = 4 * K + rho;
-      xr[K] = xN[r];
+      xr[K] = xN[4 * K + rho];
 #pragma unroll
-      for (int I = 0; I < 3; ++I) S[K][I] = Qfb[r * NX + 4 * I + kap] + Qfb[(4 * I + kap) * NX + r];
+      for (int I = 0; I < 3; ++I) S[K][I] = op.S[K][I];
     }
 #pragma unroll
     for (int I = 0; I < 3; ++I) {
@@ -524,8 +612,10 @@ constexpr int FUSED_WAVES = 4;
 constexpr int FUSED_LDS = PIPE_R * RING_SLOT + RING_LAREA;  // doubles per wave
 // BW: the backward phase's mode (lq_backward4_wave): BW4_STORE in the first iteration of a
 // fit that reuses its gains, BW4_VEC in its later ones (the gains and the factor of the
-// first, read back from a.K and a.fac), BW4_FULL otherwise. One kernel name per mode
-// (below), so a kernel trace tells them apart.
+// first, read back from a.K and a.fac), BW4_CHECK in the first iteration when the handle
+// holds an earlier fit's gains for the same μ (each wave then takes BW4_VEC or BW4_STORE by
+// its operand snapshot), BW4_FULL otherwise. One kernel name per mode (below), so a kernel
+// trace tells them apart.
 template <bool MF, int BW>
 __device__ __forceinline__ void lq_iter_fused4(const LQParams& P, int B, int T, const IterArgs& a,
                                                const LSParams& ls, double* lds_all) {
@@ -594,7 +684,8 @@ __device__ __forceinline__ void lq_iter_fused4(const LQParams& P, int B, int T, 
   }
 #endif
   if (active != 0) {
-    const unsigned nan = lq_backward4_wave<BW>(P, b0, B, active, T, a.x, a.u, a.d, a.K, a.fac, ls.mu, lds) & active;
+    const unsigned nan =
+        lq_backward4_wave<BW>(P, b0, B, active, T, a.x, a.u, a.d, a.K, a.fac, ls.mu, lds, a.snap, a.branch) & active;
     if (owner && ((nan >> q) & 1u)) {
       a.status[b0 + q] = ILQR_TRAJ_NAN;  // reference: AssertionError at backward_pass.jl:353
       if (a.res_parity) a.res_parity[b0 + q] = a.parity;
@@ -624,24 +715,30 @@ __device__ __forceinline__ void lq_iter_fused4(const LQParams& P, int B, int T, 
 ILQR_FUSED4_KERNEL(lq_iter_fused4_kernel, BW4_FULL)
 ILQR_FUSED4_KERNEL(lq_iter_fused4_store_kernel, BW4_STORE)
 ILQR_FUSED4_KERNEL(lq_iter_fused4_vec_kernel, BW4_VEC)
+ILQR_FUSED4_KERNEL(lq_iter_fused4_check_kernel, BW4_CHECK)
 #undef ILQR_FUSED4_KERNEL
 
 }  // namespace
 
 hipError_t launch_lq_iter_fused4(const LQParams& p, int B, int T, const IterArgs& a, const LSParams& ls,
-                                 hipStream_t s, bool mfma, bool vec) {
+                                 hipStream_t s, bool mfma, bool vec, bool check) {
   if (B <= 0) return hipSuccess;
   if (vec && (!a.fac || a.init)) return hipErrorInvalidValue;  // nothing to read back
+  // the checked launch is a first iteration (every present slot active: a wave that
+  // re-factors rewrites all of its gains) with a snapshot to compare against
+  if (check && (vec || !a.fac || !a.snap || !a.init)) return hipErrorInvalidValue;
   const int per_wg = FUSED_WAVES * BW4_SLOTS;
   const int grid = (B + per_wg - 1) / per_wg;
   auto go = [&](auto kernel) { kernel<<<grid, 64 * FUSED_WAVES, 0, s>>>(p, B, T, a, ls); };
-  const int bw = vec ? BW4_VEC : (a.fac ? BW4_STORE : BW4_FULL);
+  const int bw = vec ? BW4_VEC : (check ? BW4_CHECK : (a.fac ? BW4_STORE : BW4_FULL));
   if (mfma) {
     if (bw == BW4_VEC) go(lq_iter_fused4_vec_kernel<true>);
+    else if (bw == BW4_CHECK) go(lq_iter_fused4_check_kernel<true>);
     else if (bw == BW4_STORE) go(lq_iter_fused4_store_kernel<true>);
     else go(lq_iter_fused4_kernel<true>);
   } else {
     if (bw == BW4_VEC) go(lq_iter_fused4_vec_kernel<false>);
+    else if (bw == BW4_CHECK) go(lq_iter_fused4_check_kernel<false>);
     else if (bw == BW4_STORE) go(lq_iter_fused4_store_kernel<false>);
     else go(lq_iter_fused4_kernel<false>);
   }

@@ -85,6 +85,11 @@ struct IterArgs {
   double* d;            // (B, T, nu)
   double* fac;          // (ceil(B/4), T, 4, 10) the fused LQ kernel's factor of H + μI (gain reuse within
                         // one fit: written by a full backward, read by a vector-only one); nullptr: none
+  double* snap;         // (ceil(B/4), 31, 64) the operands of the matrix side that K and fac were
+                        // computed from, per wave and lane (reuse across fits: written with fac,
+                        // compared by the checked first iteration); nullptr: none kept
+  int32_t* branch;      // (ceil(B/4)) per wave of a fit's first iteration: 1 it reused the stored
+                        // gains, 0 it ran the full recursion; nullptr: not recorded
   const double* prev_cost;  // (B) in; nullptr = +Inf (fit's first iteration, forward_pass.jl:159)
   double* new_cost;         // (B) out: cost of the accepted rollout (may alias prev_cost)
   double* du2;          // (B) out, may be null
@@ -118,11 +123,16 @@ hipError_t launch_lq_iter_backward4(const LQParams& p, int B, int T, const IterA
 // backward (four trajectories per wave) + LDS-ring forward of one fit iteration in one
 // launch, (12, 4) only; the same bits as the two launches. `vec`: the backward phase
 // reuses the gains in a.K and the factor in a.fac (both written by an earlier
-// launch of the same fit with the same problem and μ) and recomputes d only: the same bits
+// launch of the same fit with the same problem and μ) and recomputes d only: the same bits.
+// `check` (a first iteration, a.init, with a.fac and a.snap of an earlier fit at the same
+// μ): each wave compares its operands with a.snap and reuses or re-factors (a.branch)
 hipError_t launch_lq_iter_fused4(const LQParams& p, int B, int T, const IterArgs& a, const LSParams& ls,
-                                 hipStream_t s, bool mfma = false, bool vec = false);
+                                 hipStream_t s, bool mfma = false, bool vec = false, bool check = false);
 // doubles of IterArgs::fac for B trajectories of T steps
 inline size_t lq_fac_doubles(size_t B, size_t T) { return (B + 3) / 4 * T * 40; }
+// waves of the fused kernel (IterArgs::branch), doubles of IterArgs::snap
+inline size_t lq_fused_waves(size_t B) { return (B + 3) / 4; }
+inline size_t lq_snap_doubles(size_t B) { return lq_fused_waves(B) * 31 * 64; }
 hipError_t launch_lq_backward_v6(int nx, int nu, const LQParams& p, int B, int T, const double* x,
                                  const double* u, double* d, double* K, int32_t* status, double mu,
                                  hipStream_t s);

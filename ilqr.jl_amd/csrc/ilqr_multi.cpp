@@ -355,6 +355,13 @@ ilqr_status ilqr_multi_fit(ilqr_multi* m, const ilqr_problem* p, const ilqr_opti
 
 int ilqr_multi_devices(const ilqr_multi* m) { return m ? (int)m->shards.size() : 0; }
 
+ilqr_status ilqr_multi_reuse_record(ilqr_multi* m, int shard, int32_t* out, int32_t capacity, int32_t* count) {
+  if (!m || shard < 0 || shard >= (int)m->shards.size() || !count) return ILQR_ERR_BAD_ARG;
+  *count = 0;
+  Shard& s = m->shards[shard];
+  return s.h ? ilqr_reuse_record(s.h, out, capacity, count) : ILQR_OK;
+}
+
 ilqr_status ilqr_host_alloc(size_t bytes, void** ptr) {
   if (!ptr) return ILQR_ERR_BAD_ARG;
   *ptr = nullptr;

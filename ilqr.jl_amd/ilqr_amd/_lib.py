@@ -41,6 +41,7 @@ SCHED_FUSED = 16
 SCHED_FORWARD_MFMA = 32
 SCHED_SEQUENTIAL_SEARCH = 64
 SCHED_FULL_BACKWARD = 128
+SCHED_REUSE_PER_CALL = 256
 MULTI_WARM_START = 1
 MULTI_USE_X_TRAJ = 2
 
@@ -128,10 +129,12 @@ SIGNATURES = {
     "ilqr_set_stream": (C.c_int, [P, P]),
     "ilqr_sync": (C.c_int, [P]),
     "ilqr_set_schedule": (C.c_int, [P, C.c_int]),
+    "ilqr_reuse_record": (C.c_int, [P, P, C.c_int32, C.POINTER(C.c_int32)]),
     "ilqr_multi_create": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "ilqr_multi_destroy": (C.c_int, [P]),
     "ilqr_multi_set_schedule": (C.c_int, [P, C.c_int]),
     "ilqr_multi_devices": (C.c_int, [P]),
+    "ilqr_multi_reuse_record": (C.c_int, [P, C.c_int, P, C.c_int32, C.POINTER(C.c_int32)]),
     "ilqr_multi_fit": (C.c_int, [P, C.POINTER(Problem), C.POINTER(Options), P, P, P, P, P, P, P, P]),
     "ilqr_multi_set_problem": (C.c_int, [P, C.POINTER(Problem)]),
     "ilqr_multi_load": (C.c_int, [P, P, P, P]),
@@ -208,6 +211,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
                           "(the HIP path has no CPU fallback)")
     lib = C.CDLL(path)
     for name, (res, args) in SIGNATURES.items():
+        if path != LIB_PATH and not hasattr(lib, name):
+            continue  # an older build loaded beside the product's (tools/ab_lib.py)
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

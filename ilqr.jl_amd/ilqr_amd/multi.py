@@ -47,15 +47,26 @@ class MultiSolver:
 
     def set_schedule(self, pipelined: bool = False, ring_forward: bool = True, backward: str = "auto",
                      fused: bool = True, forward_mfma: bool = False,
-                     sequential_search: bool = False, full_backward: bool = False):
+                     sequential_search: bool = False, full_backward: bool = False,
+                     reuse_per_call: bool = False):
         """As Solver.set_schedule, on every device's handle."""
         bk = {"auto": 0, "wave": _lib.SCHED_BACKWARD_WAVE, "block": _lib.SCHED_BACKWARD_BLOCK}[backward]
         flags = ((_lib.SCHED_PIPELINED if pipelined else 0) | (_lib.SCHED_RING_FORWARD if ring_forward else 0)
                  | bk | (_lib.SCHED_FUSED if fused and not pipelined and backward != "wave" else 0)
                  | (_lib.SCHED_FORWARD_MFMA if forward_mfma else 0)
                  | (_lib.SCHED_SEQUENTIAL_SEARCH if sequential_search else 0)
-                 | (_lib.SCHED_FULL_BACKWARD if full_backward else 0))
+                 | (_lib.SCHED_FULL_BACKWARD if full_backward else 0)
+                 | (_lib.SCHED_REUSE_PER_CALL if reuse_per_call else 0))
         _lib.check(self.lib.ilqr_multi_set_schedule(self.h, flags), "ilqr_multi_set_schedule")
+
+    def reuse_record(self, shard: int) -> np.ndarray:
+        """Solver.reuse_record of one shard's handle (ilqr_multi_reuse_record)."""
+        n = (self.batch + 3) // 4
+        out = np.zeros(n, np.int32)
+        cnt = C.c_int32(0)
+        _lib.check(self.lib.ilqr_multi_reuse_record(self.h, shard, out.ctypes.data_as(C.c_void_p), n,
+                                                    C.byref(cnt)), "ilqr_multi_reuse_record")
+        return out[:cnt.value]
 
     def fit(self, lq: LQBatch, x_init, u_init, x_traj=None, max_iter=100, tol=1e-6, mu=None,
             max_trials=None):

@@ -107,7 +107,8 @@ class Solver:
 
     def set_schedule(self, pipelined: bool = False, ring_forward: bool = True,
                      backward: str = "auto", fused: bool = True, forward_mfma: bool = False,
-                     sequential_search: bool = False, full_backward: bool = False):
+                     sequential_search: bool = False, full_backward: bool = False,
+                     reuse_per_call: bool = False):
         """LQ launch schedule (ilqr_set_schedule). pipelined: fit overlaps half of the
         workgroups' forward passes with the other half's backward passes (implies
         backward="wave"); ring_forward: the forward pass streams its inputs HBM → LDS
@@ -119,15 +120,30 @@ class Solver:
         line search trial after trial per wave instead of the cooperative search (same
         bits, include/ilqr.h); full_backward: every iteration of a fit runs the full
         backward recursion instead of reusing the first iteration's gains and factor
-        (same bits; fused path only). Schedules with the same backward kernel and forward
-        form return the same bits."""
+        (same bits; fused path only); reuse_per_call: the gains and the factor are reused
+        within one fit only, instead of staying valid for the handle's next fits as long as
+        each wave finds its part of the problem unchanged bit for bit (same bits; see
+        reuse_record). Schedules with the same backward kernel and forward form return the
+        same bits."""
         bk = {"auto": 0, "wave": _lib.SCHED_BACKWARD_WAVE, "block": _lib.SCHED_BACKWARD_BLOCK}[backward]
         flags = ((_lib.SCHED_PIPELINED if pipelined else 0) | (_lib.SCHED_RING_FORWARD if ring_forward else 0)
                  | bk | (_lib.SCHED_FUSED if fused and not pipelined and backward != "wave" else 0)
                  | (_lib.SCHED_FORWARD_MFMA if forward_mfma else 0)
                  | (_lib.SCHED_SEQUENTIAL_SEARCH if sequential_search else 0)
-                 | (_lib.SCHED_FULL_BACKWARD if full_backward else 0))
+                 | (_lib.SCHED_FULL_BACKWARD if full_backward else 0)
+                 | (_lib.SCHED_REUSE_PER_CALL if reuse_per_call else 0))
         _lib.check(self.lib.ilqr_set_schedule(self.h, flags), "ilqr_set_schedule")
+
+    def reuse_record(self) -> np.ndarray:
+        """ilqr_reuse_record: per wave (trajectories 4w .. 4w+3) of the last fit's first
+        iteration, 1 if it reused the handle's stored gains, 0 if it ran the full recursion;
+        empty if that fit kept no record. For tests and tools; synchronises."""
+        n = (self.batch + 3) // 4
+        out = np.zeros(n, np.int32)
+        cnt = C.c_int32(0)
+        _lib.check(self.lib.ilqr_reuse_record(self.h, out.ctypes.data_as(C.c_void_p), n, C.byref(cnt)),
+                   "ilqr_reuse_record")
+        return out[:cnt.value]
 
     def set_problem(self, lq):
         """lq: LQBatch (host numpy, copied to the device) or a dict of CUDA tensors

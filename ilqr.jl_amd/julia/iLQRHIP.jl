@@ -183,6 +183,7 @@ const ILQR_SCHED_FUSED = Int32(16)
 const ILQR_SCHED_FORWARD_MFMA = Int32(32)
 const ILQR_SCHED_SEQUENTIAL_SEARCH = Int32(64)
 const ILQR_SCHED_FULL_BACKWARD = Int32(128)
+const ILQR_SCHED_REUSE_PER_CALL = Int32(256)
 set_schedule!(h::Handle, flags::Integer) =
     check(ccall((:ilqr_set_schedule, libilqr), Cint, (Ptr{Cvoid}, Cint), h.ptr, flags), "ilqr_set_schedule")
 

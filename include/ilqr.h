@@ -181,13 +181,33 @@ ilqr_status ilqr_sync(ilqr_handle* h);
  *                            for the call, so the gains K_t and the factor of H + mu I
  *                            are the same in every iteration, and iterations >= 2 read
  *                            them back and recompute only d_t and the value gradient:
- *                            the same bits. Nothing is kept between
- *                            calls: every fit's first iteration reads the problem
- *                            anew. Ignored off the fused path and by ilqr_iterate /
- *                            ilqr_backward, which always run the full recursion.
+ *                            the same bits. The handle also keeps them
+ *                            for its next fit (below); with this bit nothing is kept
+ *                            or reused at all. Ignored off the fused path and by
+ *                            ilqr_iterate / ilqr_backward, which always run the full
+ *                            recursion.
+ *   ILQR_SCHED_REUSE_PER_CALL the gains and the factor are reused within one fit call
+ *                            only. Without it (the default) they outlive the call: the
+ *                            first iteration of the next fit on the handle reads the
+ *                            problem anew, and each wave (four trajectories) compares
+ *                            what the matrix side of its recursion reads (the entries of
+ *                            A, B, Q + Q', R + R', Qf + Qf') with a snapshot of the values
+ *                            its stored gains were computed from, as 64-bit patterns
+ *                            (-0.0 differs from 0.0, a NaN equals itself). A wave whose
+ *                            values are all the same runs the vector-only backward on
+ *                            the stored gains; any other wave runs the full recursion
+ *                            and refreshes its store. A problem rewritten in place or
+ *                            passed through other buffers is therefore always seen, and
+ *                            the results are the same bits either way. Another mu, an
+ *                            ilqr_iterate call, a fit on another schedule or problem
+ *                            kind, or a fit that failed with ILQR_ERR_HIP in between
+ *                            make the next fit re-factor everywhere. The snapshot takes
+ *                            the problem's own size in device memory (16 MB at batch
+ *                            4096); a caller whose problem changes with every call pays
+ *                            one read and one write of it per fit.
  * Schedules with the same backward kernel return the same bits, with or without
- * ILQR_SCHED_FULL_BACKWARD; the two backward kernels agree to rounding. Unknown bits, or BLOCK with WAVE or
- * PIPELINED → ILQR_ERR_BAD_ARG. */
+ * ILQR_SCHED_FULL_BACKWARD or ILQR_SCHED_REUSE_PER_CALL; the two backward kernels agree to
+ * rounding. Unknown bits, or BLOCK with WAVE or PIPELINED → ILQR_ERR_BAD_ARG. */
 #define ILQR_SCHED_PIPELINED 1
 #define ILQR_SCHED_RING_FORWARD 2
 #define ILQR_SCHED_BACKWARD_WAVE 4
@@ -196,7 +216,15 @@ ilqr_status ilqr_sync(ilqr_handle* h);
 #define ILQR_SCHED_FORWARD_MFMA 32
 #define ILQR_SCHED_SEQUENTIAL_SEARCH 64
 #define ILQR_SCHED_FULL_BACKWARD 128
+#define ILQR_SCHED_REUSE_PER_CALL 256
 ilqr_status ilqr_set_schedule(ilqr_handle* h, int flags);
+/* For tests and tools (not on any fit's path; synchronises the stream): what each wave of
+ * the last fit's first iteration did on the fused path with gain reuse. Wave w holds
+ * trajectories 4w .. 4w+3; out[w] = 1: it reused the handle's stored gains, 0: it ran the
+ * full recursion and stored. Copies min(capacity, *count) entries to the host array out;
+ * *count = ceil(batch / 4), or 0 if the last fit kept no record (another schedule or
+ * problem kind, ILQR_SCHED_FULL_BACKWARD). */
+ilqr_status ilqr_reuse_record(ilqr_handle* h, int32_t* out, int32_t capacity, int32_t* count);
 
 /* iLQR.backward_pass (backward_pass.jl:324-357): gains d (batch,T,nu) and
  * K (batch,T,nu,nx) for every trajectory. With a status array (batch) the call
@@ -527,6 +555,9 @@ ilqr_status ilqr_multi_create(ilqr_multi** out, const int* devices, int n_device
 ilqr_status ilqr_multi_destroy(ilqr_multi* m);
 ilqr_status ilqr_multi_set_schedule(ilqr_multi* m, int flags);
 int ilqr_multi_devices(const ilqr_multi* m);
+/* ilqr_reuse_record of shard `shard`'s handle (0 .. ilqr_multi_devices - 1; its waves count
+ * from the shard's first trajectory). */
+ilqr_status ilqr_multi_reuse_record(ilqr_multi* m, int shard, int32_t* out, int32_t capacity, int32_t* count);
 ilqr_status ilqr_multi_fit(ilqr_multi* m, const ilqr_problem* host_problem, const ilqr_options* o,
                            const double* x_init, const double* u_init, const double* x_traj,
                            double* x_out, double* u_out, double* cost, int32_t* iters,
