@@ -659,30 +659,6 @@ __device__ __forceinline__ void lq_iter_fused4(const LQParams& P, int B, int T, 
         if (b0 + q < B && a.status[b0 + q] == ILQR_TRAJ_OK) active |= 1u << q;
     }
   }
-#if ILQR_FUSED_DEPHASE_PROBE
-  // TIMING-ONLY probe (tools/archive/r05/dephase_probe.sh, not the product): half of the waves
-  // (PROBE 1: odd waves of every workgroup; 2: odd workgroups) run the forward FIRST on
-  // the gains already in K/d, then the backward — the phase mix of a de-phased schedule
-  // (forward(i−1) then backward(i) beside backward(i) then forward(i)) at one wave/SIMD.
-  // PROBE 3 is that schedule's first launch (odd waves: backward only), PROBE 4 its
-  // drain launch (odd waves: forward only, even waves nothing).
-  if (ILQR_FUSED_DEPHASE_PROBE == 3 && active != 0 && (w & 1)) {
-    (void)lq_backward4_wave<BW4_FULL>(P, b0, B, active, T, a.x, a.u, a.d, a.K, nullptr, ls.mu, lds);
-    return;
-  }
-  if (ILQR_FUSED_DEPHASE_PROBE == 4) {
-    if (active != 0 && (w & 1))
-      iter_forward_wave_active<12, 4>(P, b0, B, T, ai, ls, lds, ((active >> (l >> 4)) & 1u) != 0);
-    return;
-  }
-  if (active != 0 && ((ILQR_FUSED_DEPHASE_PROBE != 2 ? w : (int)blockIdx.x) & 1)) {
-    iter_forward_wave_active<12, 4>(P, b0, B, T, ai, ls, lds, ((active >> (l >> 4)) & 1u) != 0);
-    __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    (void)lq_backward4_wave<BW4_FULL>(P, b0, B, active, T, a.x, a.u, a.d, a.K, nullptr, ls.mu, lds);
-    return;
-  }
-#endif
   if (active != 0) {
     const unsigned nan =
         lq_backward4_wave<BW>(P, b0, B, active, T, a.x, a.u, a.d, a.K, a.fac, ls.mu, lds, a.snap, a.branch) & active;

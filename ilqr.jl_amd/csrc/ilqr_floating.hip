@@ -689,35 +689,17 @@ struct FbFwd {
 // ū = u + α·δu equals u (then every later, smaller α rolls out the same); stores x̄
 // into xn, ū into un as it goes.
 //
-// The two-barrier rollout (ILQR_FB_LOOKAHEAD=0, rounds 5-6; the pipelined one below is the
-// product) runs on three waves (fb_forward_kernel): a workgroup of three waves holds the same
-// 64 (trajectory, trial) lanes and splits each step between them —
-//   wave 0 (mass):    the mass blocks and their factors (fb_mass) of every RK4 stage, from
-//                     the stage's joint angles;
-//   wave 1 (main):    the bias of every stage (fb_bias: independent of u), then
-//                     b = ū − bias, the solve and the stage update (fb_solve), storing x̄;
-//   wave 2 (control): the step's ūₜ = uₜ + α·δuₜ + Kₜ(x̄ₜ − xₜ), its cost and Σ(ū − u)²,
-//                     storing ū — beside stage 1's mass and bias.
-// Per stage waves 0 and 2 hand the factors and ū to wave 1 through LDS, and wave 1 hands
-// back the next stage's angles (the next step's state at the last stage), between two
-// workgroup barriers. One wave alone issues a VALU instruction every 4 cycles at best,
-// so a lane's step (≈7,800 instructions on one wave) is bound by its wave's issue; the
-// three waves issue side by side. Same operations as fb_step: the same bits.
+// A workgroup of four waves (fb_forward_kernel) holds the same 64 (trajectory, trial)
+// lanes and splits each step between them, pipelined by one RK4 stage (fb_rollout3 below
+// names each wave's share). One wave alone issues a VALU instruction every 4 cycles at
+// best, so a lane's step (≈7,800 instructions on one wave) is bound by its wave's issue;
+// the four waves issue side by side and hand their pieces on through LDS. Same operations
+// as fb_step: the same bits.
 constexpr int FB_SCHUR_N = (int)(sizeof(FbSchur<double>) / sizeof(double));
 static_assert(sizeof(FbSchur<double>) == FB_SCHUR_N * sizeof(double), "FbSchur<double> is doubles only");
 constexpr int FB_CRBA_N = (int)(sizeof(FbCrba<double>) / sizeof(double));
 static_assert(sizeof(FbCrba<double>) == FB_CRBA_N * sizeof(double), "FbCrba<double> is doubles only");
-#ifndef ILQR_FB_LOOKAHEAD
-#define ILQR_FB_LOOKAHEAD 1
-#endif
-#if !ILQR_FB_LOOKAHEAD
-constexpr int FB_XU = FB_SCHUR_N;            // ū (8)
-constexpr int FB_XX = FB_SCHUR_N + FB_NU;    // the stage's state (angles; all 16 at a step's end)
-struct FbXch {
-  double v[FB_XX + FB_NX][64];  // value-major: lane l's k-th value at v[k][l]
-};
-#endif
-constexpr int FB_FWD_WAVES = ILQR_FB_LOOKAHEAD ? 4 : 3;
+constexpr int FB_FWD_WAVES = 4;
 
 // every wave reaches it: its LDS writes done (lgkmcnt only — the rollout's global stores
 // stay in flight), then the workgroup barrier
@@ -772,7 +754,6 @@ __device__ unsigned long long g_fbt[4][8];
 #define FBT_FLUSH
 #endif
 
-#if ILQR_FB_LOOKAHEAD
 // LDS writes done (lgkmcnt only), no barrier
 __device__ __forceinline__ void fb_lds_wait() {
   asm volatile("" ::: "memory");
@@ -818,10 +799,8 @@ __device__ __forceinline__ double fb_rk_next(int st, double dt, double xd, doubl
 // the same stage. The split follows tools/fb_trace.py's per-wave ticks: with fb_mass
 // and the kinematics on waves 0 and 1 (round 6's first pipeline) wave 0's rotation +
 // mass took ≈ 1.90 µs a stage and wave 1's bias + solve + update 1.81 µs, while wave 3
-// idled 1.27 µs of its 1.93. The one-stage-per-two-barriers rollout
-// (ILQR_FB_LOOKAHEAD=0) ran the rotations + bias beside the rotations + mass, then the
-// solve. Same operations, and the file built with -ffp-contract=on: the same bits
-// (DESIGN.md §4).
+// idled 1.27 µs of its 1.93. Same operations as fb_step, and the file built with
+// -ffp-contract=on: the same bits.
 constexpr int FB_IN_N = FB_NU * FB_NX + 2 * FB_NU + 2 * FB_NX;  // a step's K, u, δu, x, x_traj
 constexpr int FB_IN_S = FB_IN_N + 2;  // row stride: 16 rows' same element in distinct bank pairs
 template <int CAND>
@@ -839,7 +818,10 @@ __device__ double fb_rollout3(const FbModel& P, const FbFwd& a, int b, int T, do
     int32_t pseq[64];              // t once x̄ₜ's positions and angles are in xs (wave 3 → 2)
     double out[3][64];
   };
-  __shared__ Pipe X;  // named here: see the exchange of the two-barrier rollout below
+  // the workgroup's exchange, named here rather than passed by reference: through a
+  // reference the compiler lost its address space in some instantiations and read it
+  // with flat loads, whose waits cover the global loads in flight too
+  __shared__ Pipe X;
   FBT_DECL
   const double* x = a.x + (size_t)b * (T + 1) * FB_NX;
   const int S = 4 * T;
@@ -1126,149 +1108,6 @@ __device__ double fb_rollout3(const FbModel& P, const FbFwd& a, int b, int T, do
   FBT_FLUSH
   return cost;
 }
-#else
-template <int CAND>
-__device__ double fb_rollout3(const FbModel& P, const FbFwd& a, int b, int T, double alpha, double* __restrict__ xn,
-                              double* __restrict__ un, double& du2, bool& same, int role, int lane, bool run) {
-  // the workgroup's exchange, named here rather than passed by reference: through a
-  // reference the compiler lost its address space in some instantiations and read it
-  // with flat loads, whose waits cover the global loads in flight too
-  __shared__ FbXch X;
-  const double* x = a.x + (size_t)b * (T + 1) * FB_NX;
-  if (role == 0) {  // mass: angles in, factors out, four times a step
-    double th[FB_NX];  // only th[6], th[7] (the joint angles) are read by fb_rots
-#pragma unroll
-    for (int k = 0; k < FB_NX; ++k) th[k] = k == 6 || k == 7 ? x[k] : 0.0;
-    for (int t = 0; t < T; ++t) {
-#pragma unroll 1
-      for (int st = 0; st < 4; ++st) {
-        asm volatile("" ::: "memory");  // the model's constants re-read per stage (fb_step)
-        double R[FB_NJ][9];
-        fb_rots(P, th, R);
-        FbSchur<double> F;
-        fb_mass(P, R, F);
-        const double* f = reinterpret_cast<const double*>(&F);
-#pragma unroll
-        for (int k = 0; k < FB_SCHUR_N; ++k) X.v[k][lane] = f[k];
-        fb_lds_barrier();
-        fb_lds_barrier();
-        th[6] = X.v[FB_XX + 6][lane];
-        th[7] = X.v[FB_XX + 7][lane];
-      }
-    }
-  } else if (role == 2) {  // control: ūₜ (:72-73), its cost (:187-190), Σ(ū − u)²
-    const double* u = a.u + (size_t)b * T * FB_NU;
-    const double* xt = a.xtraj ? a.xtraj + (size_t)b * (T + 1) * FB_NX : nullptr;
-    const double* d = a.d + (size_t)b * T * FB_NU;
-    const double* K = a.K + (size_t)b * T * FB_NU * FB_NX;
-    double xb[FB_NX];
-#pragma unroll
-    for (int k = 0; k < FB_NX; ++k) xb[k] = x[k];  // x̄₁ = x₁ (:65)
-    double cost = 0.0, s2 = 0.0;
-    bool eq = true;
-    for (int t = 0; t < T; ++t) {
-      double dx[FB_NX], ub[FB_NU];
-#pragma unroll
-      for (int k = 0; k < FB_NX; ++k) dx[k] = xb[k] - x[(size_t)t * FB_NX + k];
-#pragma unroll
-      for (int j = 0; j < FB_NU; ++j) {
-        const double uj = u[(size_t)t * FB_NU + j];
-        const double ua = uj + alpha * d[(size_t)t * FB_NU + j];
-        eq = eq && ua == uj;
-        double kd = 0.0;
-#pragma unroll
-        for (int k = 0; k < FB_NX; ++k) kd = fma(K[((size_t)t * FB_NU + j) * FB_NX + k], dx[k], kd);
-        ub[j] = ua + kd;
-        X.v[FB_XU + j][lane] = ub[j];
-        const double e = ub[j] - uj;
-        s2 = fma(e, e, s2);
-      }
-#pragma unroll
-      for (int j = 0; j < FB_NU; ++j)
-        if (run) un[(size_t)t * FB_NU + j] = ub[j];
-      double ev[FB_NQ];
-#pragma unroll
-      for (int k = 0; k < FB_NQ; ++k) ev[k] = xt ? xb[k] - xt[(size_t)t * FB_NX + k] : xb[k];
-      cost = cost + stage_cost(P, ev, ub);
-#pragma unroll 1
-      for (int st = 0; st < 4; ++st) {
-        fb_lds_barrier();
-        fb_lds_barrier();
-      }
-#pragma unroll
-      for (int k = 0; k < FB_NX; ++k) xb[k] = X.v[FB_XX + k][lane];  // x̄ₜ₊₁
-    }
-    cost = cost + final_cost(P, xb);  // :192 (raw x̄_N)
-    X.v[0][lane] = cost;  // the outcome to waves 0 and 1
-    X.v[1][lane] = s2;
-    X.v[2][lane] = eq ? 1.0 : 0.0;
-  } else {  // main: bias, solve, stage update
-    double xb[FB_NX];
-#pragma unroll
-    for (int k = 0; k < FB_NX; ++k) {
-      xb[k] = x[k];
-      if (run) xn[k] = xb[k];
-    }
-    for (int t = 0; t < T; ++t) {
-      double xs[FB_NX], acc[FB_NX], ub[FB_NU];
-#pragma unroll
-      for (int i = 0; i < FB_NX; ++i) xs[i] = xb[i];
-#pragma unroll 1
-      for (int st = 0; st < 4; ++st) {
-        asm volatile("" ::: "memory");
-        double R[FB_NJ][9];
-        fb_rots(P, xs, R);
-        double bb[FB_NU];
-        fb_bias(P, R, xs, bb);
-        // the bias is complete before the barrier (else the compiler sinks it past the
-        // barrier, behind wave 0's mass, into the serial part of the stage)
-#pragma unroll
-        for (int j = 0; j < FB_NU; ++j) asm volatile("" ::"v"(bb[j]));
-        fb_lds_barrier();
-        if (st == 0) {
-#pragma unroll
-          for (int j = 0; j < FB_NU; ++j) ub[j] = X.v[FB_XU + j][lane];
-        }
-#pragma unroll
-        for (int j = 0; j < FB_NU; ++j) bb[j] = ub[j] - bb[j];
-        FbSchur<double> F;
-        double* f = reinterpret_cast<double*>(&F);
-#pragma unroll
-        for (int k = 0; k < FB_SCHUR_N; ++k) f[k] = X.v[k][lane];
-        double k[FB_NX];
-        fb_solve(F, bb, xs, k);
-        const double w = (st == 0 || st == 3) ? 1.0 : 2.0;
-        const double c = st == 2 ? 1.0 : 0.5;
-#pragma unroll
-        for (int i = 0; i < FB_NX; ++i) {
-          k[i] = P.dt * k[i];
-          acc[i] = st == 0 ? k[i] : acc[i] + w * k[i];
-          xs[i] = st < 3 ? xb[i] + k[i] * c : xb[i] + (1.0 / 6.0) * acc[i];
-        }
-        if (st < 3) {
-          X.v[FB_XX + 6][lane] = xs[6];
-          X.v[FB_XX + 7][lane] = xs[7];
-        } else {
-#pragma unroll
-          for (int i = 0; i < FB_NX; ++i) X.v[FB_XX + i][lane] = xs[i];
-        }
-        fb_lds_barrier();
-      }
-#pragma unroll
-      for (int k = 0; k < FB_NX; ++k) {
-        xb[k] = xs[k];
-        if (run) xn[(size_t)(t + 1) * FB_NX + k] = xb[k];
-      }
-    }
-  }
-  fb_lds_barrier();
-  const double cost = X.v[0][lane];
-  du2 = X.v[1][lane];
-  same = X.v[2][lane] != 0.0;
-  fb_lds_barrier();  // read before the next rollout writes
-  return cost;
-}
-#endif  // ILQR_FB_LOOKAHEAD
 
 // forward_pass for every trajectory: CAND consecutive lanes roll out trials
 // j, j+1, … at once; the first accepted trial (prev_cost − cost > 0, :77-80) is the

@@ -2,6 +2,8 @@
 # Timing-only builds of the fused iteration with half of the waves in the other phase
 # order (ILQR_FUSED_DEPHASE_PROBE, ilqr_bw4.hip): tools/fwalt/libilqr_hip_dephase{1,2,3,4}.so,
 # timed against the product by tools/archive/r05/dephase_probe.py (round 5).
+# The probe block is no longer in the product sources: run this from a tree restored by
+# tools/archive/ablation/restore_tree.sh (restore_alternates_r06.patch).
 set -e
 cd "$(dirname "$0")/../../.."
 make -C ilqr.jl_amd/csrc > /dev/null

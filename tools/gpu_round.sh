@@ -68,20 +68,6 @@ case $WHAT in
             done
             step bench100_spin 300 python bench.py --full --steps 100 --no-cpu --no-secondary
             for f in $OUT/bench20_*.log $OUT/bench100_spin.log; do python -c "import json,sys; d=[json.loads(l) for l in open(sys.argv[1]) if l.startswith('{')][-1]; print(sys.argv[1], round(d['value'],1), 'ms_per_step', round(d['ms_per_step']*1000,2), 'event_us', round(d['iteration']['event_ms']*1000,2), 'traffic', d['roofline']['traffic'])" $f; done > $OUT/wait20_ab.log; cat $OUT/wait20_ab.log ;;
-  w16ab) for i in 1 2; do
-           for v in w4 w16; do
-             ILQR_LIB=ilqr.jl_amd/lib/variants/libilqr_hip_$v.so step bench_${v}_$i 300 python tools/ab_lib.py bench.py --full --no-cpu --no-secondary
-           done
-           step bench_prod_$i 300 python bench.py --full --no-cpu --no-secondary
-         done
-         for f in $OUT/bench_w4_*.log $OUT/bench_w16_*.log $OUT/bench_prod_*.log; do python -c "import json,sys; d=[json.loads(l) for l in open(sys.argv[1]) if l.startswith('{')][-1]; print(sys.argv[1], 'value', round(d['value'],1), 'co_headline', round(d['co_headline']['value'],1), 'fit5_ms', round(d['co_headline']['ms_per_fit'],4), 'dflt', round(d['fit_default_options']['batched_it_per_s'],1), 'status5', d['fit_5_iterations']['trajectory_status_counts'])" $f; done > $OUT/w16_ab.log; cat $OUT/w16_ab.log ;;
-  tailab) for i in 1 2; do
-            for v in w4 w16; do
-              ILQR_LIB=ilqr.jl_amd/lib/variants/libilqr_hip_$v.so MODES=coop step tail_${v}_$i 200 python tools/tail_probe.py
-            done
-            MODES=coop step tail_prod_$i 200 python tools/tail_probe.py
-          done
-          grep -H "coop" $OUT/tail_*_[12].log > $OUT/tail_ab.log; cat $OUT/tail_ab.log ;;
   gatherab) for i in 1 2 3; do for wg in 0 1 4 16; do
               ILQR_GATHER_WG=$wg step ab_fit_wg${wg}_$i 120 python tools/archive/r05/ab_fit.py
             done; done
@@ -115,22 +101,6 @@ case $WHAT in
   floating) step pytest_floating 400 python -u -m pytest tests/test_gpu_floating.py -m gpu -x -v --timeout 300 --timeout-method thread
             step bench_floating 300 python tools/bench_floating.py 5 2 1 256 1024
             step rocprof_floating 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_fb -o run --output-format csv -- python tools/bench_floating.py 3 1 1 ;;
-  fbab) for i in 1 2; do
-          ILQR_LIB=ilqr.jl_amd/lib/variants/libilqr_hip_nola.so step fb_nola_$i 200 python tools/ab_lib.py tools/floating_fw_ab.py $OUT/fb_nola.npz 1 4 16 64 1024
-          step fb_la_$i 200 python tools/floating_fw_ab.py $OUT/fb_la.npz 1 4 16 64 1024
-        done
-        python tools/floating_fw_ab.py --compare $OUT/fb_nola.npz $OUT/fb_la.npz > $OUT/fb_bits.log 2>&1
-        grep -H "forward_ms\|bit_equal" $OUT/fb_nola_*.log $OUT/fb_la_*.log $OUT/fb_bits.log > $OUT/fb_ab.log; cat $OUT/fb_ab.log ;;
-  fdeepab) for i in 1 2; do
-             ILQR_LIB=ilqr.jl_amd/lib/variants/libilqr_hip_fshallow.so MODES=coop step tail_fshallow_$i 200 python tools/tail_probe.py
-             MODES=coop step tail_prod_$i 200 python tools/tail_probe.py
-           done
-           for i in 1 2; do
-             ILQR_LIB=ilqr.jl_amd/lib/variants/libilqr_hip_fshallow.so step bench_fshallow_$i 300 python tools/ab_lib.py bench.py --full --no-cpu --no-secondary
-             step bench_prod_$i 300 python bench.py --full --no-cpu --no-secondary
-           done
-           grep -H "coop" $OUT/tail_fshallow_*.log $OUT/tail_prod_*.log > $OUT/fdeep_ab.log
-           for f in $OUT/bench_fshallow_*.log $OUT/bench_prod_*.log; do python -c "import json,sys; d=[json.loads(l) for l in open(sys.argv[1]) if l.startswith('{')][-1]; print(sys.argv[1], 'value', round(d['value'],1), 'co_headline', round(d['co_headline']['value'],1), 'fit5_ms', round(d['co_headline']['ms_per_fit'],4), 'dflt', round(d['fit_default_options']['batched_it_per_s'],1))" $f; done >> $OUT/fdeep_ab.log; cat $OUT/fdeep_ab.log ;;
   fbprev) ILQR_LIB=ilqr.jl_amd/lib/variants/libilqr_hip_prev.so step fbp_prev 200 python tools/ab_lib.py tools/floating_fw_ab.py $OUT/fbp_prev.npz 1 9 70 1024
           step fbp_new 200 python tools/floating_fw_ab.py $OUT/fbp_new.npz 1 9 70 1024
           python tools/floating_fw_ab.py --compare $OUT/fbp_prev.npz $OUT/fbp_new.npz > $OUT/fbp_bits.log 2>&1
