@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/ilqr.h"
+#include "ilqr_internal.h"
 
 namespace {
 
@@ -261,6 +262,8 @@ ilqr_status ilqr_multi_fit_resident(ilqr_multi* m, const ilqr_options* o, int fl
                                     const ilqr_history* history) {
   if (!m || !m->kind || (flags & ~(ILQR_MULTI_WARM_START | ILQR_MULTI_USE_X_TRAJ)) != 0) return ILQR_ERR_BAD_ARG;
   if ((flags & ILQR_MULTI_WARM_START) ? !m->have_result : !m->loaded) return ILQR_ERR_BAD_ARG;
+  // before a warm start swaps the shards' buffers: a refused call leaves the state as it was
+  if (ilqr::check_options(o) != ILQR_OK) return ILQR_ERR_BAD_ARG;
   const ilqr_history* hist = history;
   if (hist && !hist->cost && !hist->trials && !hist->alpha && !hist->du2) hist = nullptr;
   ilqr_options def;
@@ -335,6 +338,8 @@ ilqr_status ilqr_multi_fit(ilqr_multi* m, const ilqr_problem* p, const ilqr_opti
   if (!m || !p || !x_init || !u_init || !x_out || !u_out) return ILQR_ERR_BAD_ARG;
   ilqr_status st = check_problem(m, p);
   if (st != ILQR_OK) return st;
+  // before anything is uploaded: a refused call leaves the resident problem and result valid
+  if ((st = ilqr::check_options(o)) != ILQR_OK) return st;
   // host in, host out: every call moves the problem and the trajectories both ways
   // (the device-resident calls above keep them on the devices)
   st = each_shard(m, [&](Shard& s) -> ilqr_status {

@@ -69,7 +69,7 @@ class MultiSolver:
         return out[:cnt.value]
 
     def fit(self, lq: LQBatch, x_init, u_init, x_traj=None, max_iter=100, tol=1e-6, mu=None,
-            max_trials=None):
+            max_trials=None, alpha0=None, shrink=None):
         """→ (x, u, cost, iters, status, call_status), numpy, whole batch."""
         if not isinstance(max_iter, int):
             raise TypeError("max_iter::Int64")  # forward_pass.jl:152
@@ -84,7 +84,8 @@ class MultiSolver:
         cost = np.empty(B)
         iters = np.empty(B, dtype=np.int32)
         st = np.empty(B, dtype=np.int32)
-        o = _lib.default_options(max_iter=max_iter, tol=float(tol), mu=mu, max_trials=max_trials)
+        o = _lib.default_options(max_iter=max_iter, tol=float(tol), mu=mu, max_trials=max_trials,
+                                 alpha0=alpha0, shrink=shrink)
         rc = self.lib.ilqr_multi_fit(self.h, C.byref(prob), C.byref(o), _ptr(x_init), _ptr(u_init),
                                      _ptr(xt), _ptr(xo), _ptr(uo), _ptr(cost), _ptr(iters), _ptr(st))
         _lib.check(rc, "ilqr_multi_fit", allow=(_lib.ERR_NAN, _lib.ERR_LS_EXHAUSTED))

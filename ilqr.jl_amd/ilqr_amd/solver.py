@@ -264,9 +264,10 @@ class Solver:
         _lib.check(rc, "ilqr_iterate")
 
     def fit(self, x_init, u_init, x_traj=None, max_iter=100, tol=1e-6, mu=None,
-            max_trials=None, history: bool = False) -> FitResult:
+            max_trials=None, history: bool = False, alpha0=None, shrink=None) -> FitResult:
         """iLQR.fit for the batch (synchronises). history: also return the per-iteration
-        record (ilqr_fit_ex; FitResult.history)."""
+        record (ilqr_fit_ex; FitResult.history). alpha0, shrink: the line search's first
+        step and its factor (ilqr_options; None = the defaults 1 and 0.5)."""
         if not isinstance(max_iter, int):
             raise TypeError("max_iter::Int64")  # forward_pass.jl:152
         B, T, nx, nu = self.batch, self.T, self.nx, self.nu
@@ -279,7 +280,8 @@ class Solver:
         iters = torch.empty((B,), dtype=torch.int32, device=self.dev)
         st = torch.empty((B,), dtype=torch.int32, device=self.dev)
         self._bind_stream()
-        o = _lib.default_options(max_iter=max_iter, tol=float(tol), mu=mu, max_trials=max_trials)
+        o = _lib.default_options(max_iter=max_iter, tol=float(tol), mu=mu, max_trials=max_trials,
+                                 alpha0=alpha0, shrink=shrink)
         hist, hst = alloc_history(max_iter, B, self.dev) if history else (None, None)
         rc = self.lib.ilqr_fit_ex(self.h, self._p(), C.byref(o), _ptr(x_init), _ptr(u_init),
                                   _ptr(x_traj), _ptr(xo), _ptr(uo), _ptr(cost), _ptr(iters), _ptr(st),

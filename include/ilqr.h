@@ -303,7 +303,9 @@ ilqr_status ilqr_fit(ilqr_handle* h, const ilqr_problem* p, const ilqr_options* 
  *   cost    the accepted rollout's cost (the printed Total Cost); NaN when the
  *           trajectory did not run iteration i (it had stopped) or its search failed
  *   trials  line-search trials of iteration i (0: did not run)
- *   alpha   the accepted step α = alpha0·shrink^(trials−1) (NaN as for cost)
+ *   alpha   the accepted step α: alpha0 multiplied by shrink trials−1 times in turn, the
+ *           repeated product the search itself used, bit for bit (not alpha0 times a
+ *           power of shrink, which rounds otherwise; NaN as for cost)
  *   du2     Σ(ū − u)² of the iteration's last trial, the convergence test's quantity
  *           (:171; NaN: did not run)
  * Entries past a fit's last iteration (every trajectory stopped, or the poll broke

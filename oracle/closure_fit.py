@@ -62,7 +62,10 @@ def derivative_tiles(x, u, dynamicsf, quad, fquad):
     nb, N, nx = x.shape
     T, nu = u.shape[1], u.shape[2]
     xs, us = x[:, :T].reshape(-1, nx), u.reshape(-1, nu)
-    A, Bm = jet.jacobians(dynamicsf, xs, us)                          # :32-33
+    if hasattr(dynamicsf, "jacobians"):   # a closure that carries its own exact batched Jacobians
+        A, Bm = dynamicsf.jacobians(xs, us)
+    else:
+        A, Bm = jet.jacobians(dynamicsf, xs, us)                      # :32-33
     lx, lu, lxx, lux, luu = quad(xs, us)                               # :95-99
     lfx, lfxx = fquad(x[:, T])                                         # :142-143
     r = lambda a, *s: np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape((nb,) + s))  # noqa: E731
@@ -113,7 +116,7 @@ def forward_pass(x, u, x_traj, d, K, prev_cost, dynamicsf, immediate_cost, final
 
 
 def fit(x_init, u_init, dynamicsf, immediate_cost, final_cost, quad, fquad, x_traj=None,
-        max_iter=100, tol=1e-6, max_trials=64, mu=0.01):
+        max_iter=100, tol=1e-6, max_trials=64, mu=0.01, alpha0=1.0, shrink=0.5):
     """fit (forward_pass.jl:148-179) for a batch → dict(x, u, cost, iters, status,
     history), status as include/ilqr.h's ilqr_traj_status: 1 converged, 2 max_iter,
     3 line search exhausted, 4 NaN."""
@@ -133,7 +136,7 @@ def fit(x_init, u_init, dynamicsf, immediate_cost, final_cost, quad, fquad, x_tr
         status = np.where(run & (bst == 4), 4, status)
         run = status == 0
         xn, un, c, ntr, ok = forward_pass(xi, ui, xt, d, K, prev, dynamicsf, immediate_cost,
-                                          final_cost, max_trials)                    # :163-166
+                                          final_cost, max_trials, alpha0, shrink)    # :163-166
         iters = np.where(run, it, iters)
         bad = run & ~ok
         status = np.where(bad, np.where(np.isnan(c), 4, 3), status)

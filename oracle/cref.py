@@ -76,8 +76,11 @@ def lq_forward(lq, x, u, x_traj, d, K, prev_cost, max_trials=64, alpha0=1.0, shr
 
 
 def lq_fit(lq, x_init, u_init, x_traj=None, max_iter=100, tol=1e-6, mu=0.01, max_trials=64,
-           symmetrize=False, nthreads=0):
-    """→ (x, u, cost, iters, status)   status: 1 converged, 2 max_iter, 3 LS exhausted, 4 NaN"""
+           symmetrize=False, nthreads=0, alpha0=1.0, shrink=0.5, history=False):
+    """→ (x, u, cost, iters, status)   status: 1 converged, 2 max_iter, 3 LS exhausted, 4 NaN;
+    with history=True also tl_fit's per-iteration record and "gap": the closest any trial's cost
+    of that iteration came to prev_cost, relative to it (Inf at prev_cost = Inf) — how far the
+    iteration's accept/reject decisions were from flipping."""
     lib = load()
     nb, n, m = lq.B.shape
     T = u_init.shape[1]
@@ -88,9 +91,16 @@ def lq_fit(lq, x_init, u_init, x_traj=None, max_iter=100, tol=1e-6, mu=0.01, max
     cost = np.empty(nb)
     iters = np.empty(nb, dtype=np.int32)
     st = np.empty(nb, dtype=np.int32)
-    lib.oracle_lq_fit(nb, T, n, m, _p(lq.A), _p(lq.B), _p(lq.Q), _p(lq.R), _p(lq.Qf), _p(xi),
+    h = None
+    if history:
+        h = {"cost": np.full((nb, max_iter), np.nan), "trials": np.zeros((nb, max_iter), dtype=np.int32),
+             "du2": np.full((nb, max_iter), np.nan), "gap": np.full((nb, max_iter), np.nan)}
+    lib.oracle_lq_fit_opt(nb, T, n, m, _p(lq.A), _p(lq.B), _p(lq.Q), _p(lq.R), _p(lq.Qf), _p(xi),
                       _p(ui), _p(xt), max_iter, C.c_double(tol), C.c_double(mu), int(symmetrize), max_trials,
-                      _p(xo), _p(uo), _p(cost), _p(iters), _p(st), nthreads)
+                      C.c_double(alpha0), C.c_double(shrink), _p(xo), _p(uo), _p(cost), _p(iters), _p(st),
+                      nthreads, *((_p(h["cost"]), _p(h["trials"]), _p(h["du2"]), _p(h["gap"])) if h else (None,) * 4))
+    if history:
+        return xo, uo, cost, iters, st, {k: np.ascontiguousarray(v.T) for k, v in h.items()}
     return xo, uo, cost, iters, st
 
 
@@ -132,7 +142,7 @@ def tl_forward(x, u, x_traj, d, K, prev_cost, max_trials=64, alpha0=1.0, shrink=
 
 
 def tl_fit(x_init, u_init, x_traj=None, max_iter=100, tol=1e-6, mu=0.01, max_trials=64,
-           symmetrize=False, nthreads=0, history=False):
+           symmetrize=False, nthreads=0, history=False, alpha0=1.0, shrink=0.5):
     """→ (x, u, cost, iters, status), plus with history=True a dict of (max_iter, B)
     arrays "cost" (NaN: not run / failed), "trials" (0: not run), "du2" — the layout of
     ilqr_fit_ex's record (include/ilqr.h)."""
@@ -149,9 +159,9 @@ def tl_fit(x_init, u_init, x_traj=None, max_iter=100, tol=1e-6, mu=0.01, max_tri
     if history:
         h = {"cost": np.full((nb, max_iter), np.nan), "trials": np.zeros((nb, max_iter), dtype=np.int32),
              "du2": np.full((nb, max_iter), np.nan)}
-    lib.oracle_tl_fit(nb, T, nu, _p(xi), _p(ui), _p(xt), max_iter, C.c_double(tol), C.c_double(mu),
-                      int(symmetrize), max_trials, _p(xo), _p(uo), _p(cost), _p(iters), _p(st),
-                      nthreads, *((_p(h["cost"]), _p(h["trials"]), _p(h["du2"])) if h else (None, None, None)))
+    lib.oracle_tl_fit_opt(nb, T, nu, _p(xi), _p(ui), _p(xt), max_iter, C.c_double(tol), C.c_double(mu),
+                      int(symmetrize), max_trials, C.c_double(alpha0), C.c_double(shrink), _p(xo), _p(uo),
+                      _p(cost), _p(iters), _p(st), nthreads, *((_p(h["cost"]), _p(h["trials"]), _p(h["du2"])) if h else (None, None, None)))
     if history:
         return xo, uo, cost, iters, st, {k: np.ascontiguousarray(v.T) for k, v in h.items()}
     return xo, uo, cost, iters, st
@@ -235,7 +245,8 @@ def chain_dynamics(pr, x, u):
     return out
 
 
-def chain_iterate(pr, x, u, mu=0.01, symmetrize=True, max_trials=64, nthreads=0):
+def chain_iterate(pr, x, u, mu=0.01, symmetrize=True, max_trials=64, nthreads=0, alpha0=1.0,
+                  shrink=0.5):
     """One cold-start iteration per trajectory (central-difference linearisation,
     backward_pass, forward_pass) → (d, K, x_new, u_new, cost, trials)."""
     lib = load()
@@ -248,8 +259,8 @@ def chain_iterate(pr, x, u, mu=0.01, symmetrize=True, max_trials=64, nthreads=0)
     cost = np.empty(nb)
     trials = np.empty(nb, dtype=np.int32)
     args, keep = _chain_args(pr)
-    rc = lib.oracle_chain_iterate(nb, T, *args, _p(x), _p(u), C.c_double(mu), int(symmetrize),
-                                  max_trials, _p(d), _p(K), _p(xn), _p(un), _p(cost), _p(trials),
-                                  nthreads)
+    rc = lib.oracle_chain_iterate_opt(nb, T, *args, _p(x), _p(u), C.c_double(mu), int(symmetrize),
+                                  max_trials, C.c_double(alpha0), C.c_double(shrink), _p(d), _p(K),
+                                  _p(xn), _p(un), _p(cost), _p(trials), nthreads)
     assert rc >= 0, "oracle_chain_iterate: bad chain"
     return d, K, xn, un, cost, trials

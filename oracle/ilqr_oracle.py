@@ -197,7 +197,8 @@ def forward_pass(x, u, x_traj, dus, Ks, prev_cost, dynamicsf, immediate_cost, fi
 # L4 driver
 # --------------------------------------------------------------------------------
 def fit(x_init, u_init, dynamicsf, immediate_cost, final_cost, x_traj=None,
-        max_iter=100, tol=1e-6, max_trials=None, history=None, mu=REG_MU, symmetrize=False):
+        max_iter=100, tol=1e-6, max_trials=None, history=None, mu=REG_MU, symmetrize=False,
+        alpha0=1.0, shrink=0.5):
     """src/forward_pass.jl:148-179.
 
     Quirks kept: prev_cost starts at Inf (so iteration 1 accepts α=1 whenever
@@ -218,12 +219,13 @@ def fit(x_init, u_init, dynamicsf, immediate_cost, final_cost, x_traj=None,
         st = {}
         xn, un, new_cost = forward_pass(xi, ui, x_traj, dus, Ks, prev_cost, dynamicsf,
                                         immediate_cost, final_cost, max_trials=max_trials,
-                                        stats=st)                      # :163-166
+                                        alpha0=alpha0, shrink=shrink, stats=st)  # :163-166
         assert prev_cost > new_cost                                    # :168
         prev_cost = new_cost
         du2 = float(np.sum((un - ui) ** 2))
         if history is not None:
-            history.append({"iter": it, "cost": new_cost, "trials": st["trials"], "du2": du2})
+            history.append({"iter": it, "cost": new_cost, "trials": st["trials"], "du2": du2,
+                            "alpha": st["alpha"]})
         if du2 <= tol:                                                 # :171
             break
         xi, ui = xn, un                                                # :174-175

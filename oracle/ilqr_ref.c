@@ -489,15 +489,18 @@ static int backward_one(const prob_t* P, const double* x, const double* u, doubl
   return nan;
 }
 
-/* forward_pass (forward_pass.jl:55-93). Returns trials (>0 accepted, <0 exhausted). */
+/* forward_pass (forward_pass.jl:55-93). Returns trials (>0 accepted, <0 exhausted). gap_out (may
+ * be NULL): the closest any trial's cost came to prev_cost, relative to it (Inf for an infinite
+ * prev_cost) — how far the search's decisions were from flipping. */
 static int forward_one(const prob_t* P, const double* x, const double* u, const double* xtraj,
                        const double* d, const double* K, double prev_cost, double* xb,
                        double* ub, double* cost_out, int max_trials, double alpha0,
-                       double shrink) {
+                       double shrink, double* gap_out) {
   const int n = P->n, m = P->m, T = P->T;
   double alpha = alpha0;
   double dx[NMAX], e[NMAX], Kdx[MMAX];
-  double new_cost = 0.0;
+  double new_cost = 0.0, gap = INFINITY;
+  if (gap_out) *gap_out = gap;
   for (int trial = 1; trial <= max_trials; ++trial) {
     memcpy(xb, x, sizeof(double) * n); /* :65 */
     for (int k = 0; k < T; ++k) {      /* :71 */
@@ -516,8 +519,10 @@ static int forward_one(const prob_t* P, const double* x, const double* u, const 
     acc += P->fcost(P, xb + (size_t)T * n);
     new_cost = acc;
     *cost_out = new_cost;
+    if (gap_out && isfinite(prev_cost) && fabs(prev_cost - new_cost) / fabs(prev_cost) < gap)
+      *gap_out = gap = fabs(prev_cost - new_cost) / fabs(prev_cost);
     if (prev_cost - new_cost > 0) return trial; /* :77-80 */
-    alpha /= 1.0 / shrink;                     /* :82 α /= 2 */
+    alpha *= shrink;                           /* :82 α /= 2 (α *= shrink: the header's rule) */
   }
   return -max_trials;
 }
@@ -838,7 +843,7 @@ int oracle_lq_forward(int Bn, int T, int n, int m, const double* A, const double
                                xtraj ? xtraj + (size_t)b * (T + 1) * n : NULL,
                                d + (size_t)b * T * m, K + (size_t)b * T * m * n, prev_cost[b],
                                xnew + (size_t)b * (T + 1) * n, unew + (size_t)b * T * m, &cost[b],
-                               max_trials, alpha0, shrink);
+                               max_trials, alpha0, shrink, NULL);
     if (trials) trials[b] = tr;
     fails += tr < 0;
   }
@@ -858,8 +863,9 @@ void oracle_set_fit_return_post_update(int on) { FIT_RETURN_POST_UPDATE = on; }
 
 static void fit_one(const prob_t* P, const double* x_init, const double* u_init,
                     const double* xtraj, int max_iter, double tol, double mu, int sym,
-                    int max_trials, double* x_out, double* u_out, double* cost, int* iters,
-                    int* status, double* hcost, int* htrials, double* hdu2) {
+                    int max_trials, double alpha0, double shrink, double* x_out, double* u_out,
+                    double* cost, int* iters, int* status, double* hcost, int* htrials,
+                    double* hdu2, double* hgap) {
   const int n = P->n, m = P->m, T = P->T;
   const size_t xs = (size_t)(T + 1) * n, us = (size_t)T * m;
   double* buf = (double*)malloc(sizeof(double) * (2 * xs + 2 * us + us + us * n));
@@ -870,8 +876,10 @@ static void fit_one(const prob_t* P, const double* x_init, const double* u_init,
   int st = 2, it;
   for (it = 1; it <= max_iter; ++it) { /* :161 */
     if (backward_one(P, xi, ui, mu, sym, d, K)) { st = 4; break; }
-    double nc = NAN;
-    const int tr = forward_one(P, xi, ui, xtraj, d, K, prev_cost, xn, un, &nc, max_trials, 1.0, 0.5);
+    double nc = NAN, gap = INFINITY;
+    const int tr = forward_one(P, xi, ui, xtraj, d, K, prev_cost, xn, un, &nc, max_trials, alpha0, shrink,
+                               &gap);
+    if (hgap) hgap[it - 1] = gap;
     if (htrials) htrials[it - 1] = tr < 0 ? max_trials : tr;
     if (hcost) hcost[it - 1] = tr < 0 ? NAN : nc;
     if (tr < 0) { st = (nc != nc) ? 4 : 3; break; }
@@ -898,22 +906,38 @@ static void fit_one(const prob_t* P, const double* x_init, const double* u_init,
   free(buf);
 }
 
+/* The fits and the chain iteration at the caller's alpha0 and shrink are the *_opt entries; the
+ * entries of the earlier names keep their argument lists and run them at the defaults (1, 0.5).
+ * History arrays (may be NULL) as oracle_tl_fit's; hgap: forward_one's gap of every iteration. */
+int oracle_lq_fit_opt(int Bn, int T, int n, int m, const double* A, const double* Bm, const double* Q,
+                  const double* R, const double* Qf, const double* x_init, const double* u_init,
+                  const double* xtraj, int max_iter, double tol, double mu, int sym, int max_trials,
+                  double alpha0, double shrink, double* x_out, double* u_out, double* cost,
+                  int* iters, int* status, int nthreads, double* hcost, int* htrials,
+                  double* hdu2, double* hgap) {
+  if (n > NMAX || m > MMAX) return -1;
+  set_threads(nthreads);
+  const size_t xs = (size_t)(T + 1) * n, us = (size_t)T * m, hs = (size_t)max_iter;
+#pragma omp parallel for schedule(dynamic, 4)
+  for (int b = 0; b < Bn; ++b) {
+    const prob_t P = instance(b, n, m, T, A, Bm, Q, R, Qf);
+    fit_one(&P, x_init + b * xs, u_init + b * us, xtraj ? xtraj + b * xs : NULL, max_iter, tol, mu,
+            sym, max_trials, alpha0, shrink, x_out + b * xs, u_out + b * us, &cost[b],
+            iters ? &iters[b] : NULL,
+            status ? &status[b] : NULL, hcost ? hcost + b * hs : NULL, htrials ? htrials + b * hs : NULL,
+            hdu2 ? hdu2 + b * hs : NULL, hgap ? hgap + b * hs : NULL);
+  }
+  return 0;
+}
+
 int oracle_lq_fit(int Bn, int T, int n, int m, const double* A, const double* Bm, const double* Q,
                   const double* R, const double* Qf, const double* x_init, const double* u_init,
                   const double* xtraj, int max_iter, double tol, double mu, int sym, int max_trials,
                   double* x_out, double* u_out, double* cost, int* iters, int* status,
                   int nthreads) {
-  if (n > NMAX || m > MMAX) return -1;
-  set_threads(nthreads);
-  const size_t xs = (size_t)(T + 1) * n, us = (size_t)T * m;
-#pragma omp parallel for schedule(dynamic, 4)
-  for (int b = 0; b < Bn; ++b) {
-    const prob_t P = instance(b, n, m, T, A, Bm, Q, R, Qf);
-    fit_one(&P, x_init + b * xs, u_init + b * us, xtraj ? xtraj + b * xs : NULL, max_iter, tol, mu,
-            sym, max_trials, x_out + b * xs, u_out + b * us, &cost[b], iters ? &iters[b] : NULL,
-            status ? &status[b] : NULL, NULL, NULL, NULL);
-  }
-  return 0;
+  return oracle_lq_fit_opt(Bn, T, n, m, A, Bm, Q, R, Qf, x_init, u_init, xtraj, max_iter, tol, mu, sym,
+                           max_trials, 1.0, 0.5, x_out, u_out, cost, iters, status, nthreads, NULL, NULL,
+                           NULL, NULL);
 }
 
 /* -- 2-link arm entry points (same conventions as the LQ ones) -- */
@@ -944,7 +968,7 @@ int oracle_tl_forward(int Bn, int T, int nu, const double* x, const double* u, c
     const int tr = forward_one(&P, x + (size_t)b * (T + 1) * 4, u + (size_t)b * T * nu,
                                xtraj ? xtraj + (size_t)b * (T + 1) * 4 : NULL, d + (size_t)b * T * nu,
                                K + (size_t)b * T * nu * 4, prev_cost[b], xnew + (size_t)b * (T + 1) * 4,
-                               unew + (size_t)b * T * nu, &cost[b], max_trials, alpha0, shrink);
+                               unew + (size_t)b * T * nu, &cost[b], max_trials, alpha0, shrink, NULL);
     if (trials) trials[b] = tr;
     fails += tr < 0;
   }
@@ -952,20 +976,29 @@ int oracle_tl_forward(int Bn, int T, int nu, const double* x, const double* u, c
 }
 
 /* history arrays (may be NULL): (Bn, max_iter), trajectory slowest (see fit_one) */
-int oracle_tl_fit(int Bn, int T, int nu, const double* x_init, const double* u_init, const double* xtraj,
-                  int max_iter, double tol, double mu, int sym, int max_trials, double* x_out,
-                  double* u_out, double* cost, int* iters, int* status, int nthreads, double* hcost,
-                  int* htrials, double* hdu2) {
+int oracle_tl_fit_opt(int Bn, int T, int nu, const double* x_init, const double* u_init, const double* xtraj,
+                  int max_iter, double tol, double mu, int sym, int max_trials, double alpha0,
+                  double shrink, double* x_out, double* u_out, double* cost, int* iters, int* status,
+                  int nthreads, double* hcost, int* htrials, double* hdu2) {
   set_threads(nthreads);
   const prob_t P = tl_problem(T, nu);
   const size_t xs = (size_t)(T + 1) * 4, us = (size_t)T * nu, hs = (size_t)max_iter;
 #pragma omp parallel for schedule(dynamic, 4)
   for (int b = 0; b < Bn; ++b)
     fit_one(&P, x_init + b * xs, u_init + b * us, xtraj ? xtraj + b * xs : NULL, max_iter, tol, mu,
-            sym, max_trials, x_out + b * xs, u_out + b * us, &cost[b], iters ? &iters[b] : NULL,
+            sym, max_trials, alpha0, shrink, x_out + b * xs, u_out + b * us, &cost[b],
+            iters ? &iters[b] : NULL,
             status ? &status[b] : NULL, hcost ? hcost + b * hs : NULL, htrials ? htrials + b * hs : NULL,
-            hdu2 ? hdu2 + b * hs : NULL);
+            hdu2 ? hdu2 + b * hs : NULL, NULL);
   return 0;
+}
+
+int oracle_tl_fit(int Bn, int T, int nu, const double* x_init, const double* u_init, const double* xtraj,
+                  int max_iter, double tol, double mu, int sym, int max_trials, double* x_out,
+                  double* u_out, double* cost, int* iters, int* status, int nthreads, double* hcost,
+                  int* htrials, double* hdu2) {
+  return oracle_tl_fit_opt(Bn, T, nu, x_init, u_init, xtraj, max_iter, tol, mu, sym, max_trials, 1.0, 0.5,
+                           x_out, u_out, cost, iters, status, nthreads, hcost, htrials, hdu2);
 }
 
 /* backward_pass on caller-supplied tiles (ilqr_backward_tiles' checker). x/u are
@@ -1011,9 +1044,9 @@ int oracle_chain_dynamics(int npts, CH_ARGS, const double* x, const double* u, d
 
 /* one cold-start fit iteration per trajectory (prev_cost = +Inf): backward_pass on the
  * central-difference linearisation, then forward_pass with the line search. */
-int oracle_chain_iterate(int Bn, int T, CH_ARGS, const double* x, const double* u, double mu,
-                         int sym, int max_trials, double* d, double* K, double* xn, double* un,
-                         double* cost, int* trials, int nthreads) {
+int oracle_chain_iterate_opt(int Bn, int T, CH_ARGS, const double* x, const double* u, double mu,
+                         int sym, int max_trials, double alpha0, double shrink, double* d, double* K,
+                         double* xn, double* un, double* cost, int* trials, int nthreads) {
   chain_t C;
   if (ch_init(&C, CH_PASS) != 0) return -1;
   set_threads(nthreads);
@@ -1027,8 +1060,15 @@ int oracle_chain_iterate(int Bn, int T, CH_ARGS, const double* x, const double* 
     const int bad = backward_one(&P, x + b * xs, u + b * us, mu, sym, d + b * us, K + b * us * n);
     nans += bad;
     const int tr = forward_one(&P, x + b * xs, u + b * us, NULL, d + b * us, K + b * us * n, INFINITY,
-                               xn + b * xs, un + b * us, &cost[b], max_trials, 1.0, 0.5);
+                               xn + b * xs, un + b * us, &cost[b], max_trials, alpha0, shrink, NULL);
     if (trials) trials[b] = tr;
   }
   return nans;
+}
+
+int oracle_chain_iterate(int Bn, int T, CH_ARGS, const double* x, const double* u, double mu,
+                         int sym, int max_trials, double* d, double* K, double* xn, double* un,
+                         double* cost, int* trials, int nthreads) {
+  return oracle_chain_iterate_opt(Bn, T, CH_PASS, x, u, mu, sym, max_trials, 1.0, 0.5, d, K, xn, un, cost,
+                                  trials, nthreads);
 }

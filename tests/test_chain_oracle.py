@@ -417,3 +417,54 @@ def test_coupled_six_fixtures_consistent(gen6):
             cost += l(list(x[t]), list(u[t]))
         cost += lf(list(x[-1]))
         assert abs(cost - z["fw_cost"][1]) <= 1e-14 * abs(cost), (name, cost, z["fw_cost"][1])
+
+
+# -- the batched chain oracle (oracle/chain_batch.py) -----------------------------------------
+@pytest.mark.parametrize("case", ["coupled2", "chain4_goal_per_trajectory", "chain4_task"])
+def test_batched_chain_oracle_matches_per_trajectory_oracle(case):
+    """oracle.chain_batch.ChainOracle (Jacobians of all points at once, rollouts by the C
+    restatement, the C recursion, closure_fit's search) against the per-trajectory oracle
+    (oracle.rbd's closures through oracle.ilqr_oracle) at μ = 0.05, alpha0 = 0.9, shrink = 0.7:
+    gains 1e-11, a searched forward pass and a 3-iteration fit with the same trial counts, iterates
+    1e-10 — under the joint-space costs, a goal per trajectory and the task-space costs."""
+    from ilqr_amd.chain import coupled_2dof_problem, coupled_chain_problem
+    from oracle import cost_functions as OC
+    from oracle import ilqr_oracle as O
+    from oracle import rbd
+    from oracle.chain_batch import ChainOracle
+    rel = lambda a, b: float(np.abs(np.asarray(a) - np.asarray(b)).max() / np.abs(b).max())  # noqa: E731
+    pr = coupled_2dof_problem(2) if case == "coupled2" else coupled_chain_problem(4)
+    n, nb, T = pr.n_joints, 2, 8
+    targets = task = None
+    if case == "chain4_goal_per_trajectory":
+        targets = np.asarray(pr.target, float) + np.array([[0.0] * n, [0.35, -0.25, 0.3, -0.4]])
+    if case == "chain4_task":
+        task = dict(body=n - 1, point=[0.05, 0.02, 0.1], final_target=[1.9, 0.9, 1.0], weight=2e3, euclidean=True)
+    orc = ChainOracle(pr, T, targets=targets, task=task)
+    rng = np.random.default_rng(5)
+    x0 = np.concatenate([rng.uniform(-1, 1, (nb, n)), rng.uniform(-0.5, 0.5, (nb, n))], axis=1)
+    u = rng.uniform(-0.5, 0.5, (nb, T, pr.nu))
+    x = orc.rollout(x0, u)
+    (d, K), = orc.backward(x, u, [0.05])
+    pc = orc.l(x[:, :T].reshape(-1, 2 * n), u.reshape(-1, pr.nu)).reshape(nb, T).sum(1) + orc.lf(x[:, T])
+    fw = orc.forward(x, u, 6.0 * d, K, pc, max_trials=64, alpha0=0.9, shrink=0.7)
+    fit = orc.fit(x, u, max_iter=3, tol=-1.0, mu=0.05, alpha0=0.9, shrink=0.7)
+    model = rbd.ChainModel(pr.chain, pr.dt)
+    for b in range(nb):
+        cost = rbd.ChainCost(pr.target if targets is None else targets[b], pr.q_weight, pr.r_weight, pr.qf_weight)
+        f, l, lf = rbd.chain_closures(model, cost)
+        if task is not None:
+            a = (pr.chain, task["body"], task["point"], task["final_target"], task["weight"])
+            l, lf = OC.simple_immediate_cost(*a), OC.simple_final_cost(*a, euclidean=True)
+        do, Ko = O.backward_pass(x[b], u[b], f, l, lf, mu=0.05, symmetrize=True)
+        assert rel(d[b], do) < 1e-11 and rel(K[b], Ko) < 1e-11, (b, rel(d[b], do), rel(K[b], Ko))
+        st = {}
+        xo, uo, co = O.forward_pass(x[b], u[b], np.zeros_like(x[b]), 6.0 * d[b], K[b], pc[b], f, l, lf, max_trials=64,
+                                    alpha0=0.9, shrink=0.7, stats=st)
+        assert fw[3][b] == st["trials"] and rel(fw[1][b], uo) < 1e-10 and abs(fw[2][b] - co) < 1e-10 * abs(co), b
+        h = []
+        xf, uf = O.fit(x[b], u[b], f, l, lf, max_iter=3, tol=-1.0, max_trials=64, history=h, mu=0.05, symmetrize=True,
+                       alpha0=0.9, shrink=0.7)
+        assert fit["history"]["trials"][:, b].tolist() == [e["trials"] for e in h], b
+        assert rel(fit["u"][b], uf) < 1e-10 and rel(fit["x"][b], xf) < 1e-10, b
+    assert (fw[3] > 1).any()     # the forward pass did search

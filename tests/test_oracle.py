@@ -237,3 +237,109 @@ def test_c_oracle_twolink_nu1_agrees_with_golden():
     xo, uo, co, it, st = cref.tl_fit(g["x"], g["u"], max_iter=40)
     assert np.array_equal(it, g["fit_iters"]) and (st == 1).all()
     assert rel(xo, g["fit_x"]) < 1e-12 and rel(uo, g["fit_u"]) < 1e-12
+
+
+# -- the line search off its default options ------------------------------------------
+def _repeated_product(alpha0, shrink, trial):
+    """α of trial j: alpha0 multiplied by shrink j − 1 times in turn (forward_pass.jl:82)."""
+    a = alpha0
+    for _ in range(trial - 1):
+        a *= shrink
+    return a
+
+
+def _lq_search_case():
+    g = np.load(os.path.join(GOLD, "quad_t16.npz"), allow_pickle=False)
+    from ilqr_amd.problems import LQBatch
+    lq = LQBatch(g["A"], g["B"], g["Q"], g["R"], g["Qf"])
+    nb = lq.batch
+    scales = np.array([1, 3, 6, 12, 24, 48, 96, 400], dtype=float)[np.arange(nb) % 8]
+    x, u, K = g["x"], g["u"], g["K"]
+    d = g["d"] * scales[:, None, None]
+    cl = [O.lq_closures(lq.A[b], lq.B[b], lq.Q[b], lq.R[b], lq.Qf[b]) for b in range(nb)]
+    pc = np.array([O.total_cost_generator(np.zeros_like(x[b]), cl[b][1], cl[b][2])(x[b], u[b]) for b in range(nb)])
+    py = lambda b, **kw: O.forward_pass(x[b], u[b], np.zeros_like(x[b]), d[b], K[b], pc[b], *cl[b], **kw)  # noqa: E731
+    c = lambda **kw: cref.lq_forward(lq, x, u, None, d, K, kw.pop("prev_cost", pc), **kw)  # noqa: E731
+    return nb, py, c
+
+
+def _tl_search_case(nu):
+    g = np.load(os.path.join(GOLD, "twolink_t50.npz" if nu == 2 else "twolink_nu1_t50.npz"), allow_pickle=False)
+    TL = O.TwoLink
+    f = TL.dynamicsf if nu == 2 else TL.dynamicsf_nu1
+    scales = np.array([1, 3, 6, 12, 24, 48, 96, 3, 400], dtype=float)   # test_gpu_twolink's search case
+    idx = np.arange(len(scales)) % g["u"].shape[0]
+    x, u, K = g["x"][idx], g["u"][idx], g["K"][idx]
+    d = g["d"][idx] * scales[:, None, None]
+    pc = np.array([O.total_cost_generator(np.zeros_like(x[b]), TL.immediate_cost, TL.final_cost)(x[b], u[b])
+                   for b in range(len(idx))])
+    py = lambda b, **kw: O.forward_pass(x[b], u[b], np.zeros_like(x[b]), d[b], K[b], pc[b], f,  # noqa: E731
+                                        TL.immediate_cost, TL.final_cost, **kw)
+    c = lambda **kw: cref.tl_forward(x, u, None, d, K, kw.pop("prev_cost", pc), **kw)  # noqa: E731
+    return len(idx), py, c
+
+
+@pytest.mark.parametrize("case", ["lq", "tl_nu2", "tl_nu1"])
+def test_forward_pass_off_default_options_numpy_vs_c(case):
+    """forward_pass at alpha0 = 0.9, shrink = 0.7 (no step a power of two): the numpy and the C
+    restatement accept at the same trial and agree on the rollout to 1e-12, and the α of
+    trial j is alpha0 multiplied by shrink j − 1 times in turn, bit for bit — the numpy
+    oracle's by its own record, the C oracle's by its accepted rollout being, bit for bit,
+    the one trial it runs from that product as alpha0 (a one-ulp change of α moves ū)."""
+    a0, sh = 0.9, 0.7
+    nb, py, c = {"lq": _lq_search_case, "tl_nu2": lambda: _tl_search_case(2),
+                 "tl_nu1": lambda: _tl_search_case(1)}[case]()
+    xc, uc, cc, trc = c(alpha0=a0, shrink=sh)
+    seen = set()
+    for b in range(nb):
+        st = {}
+        xo, uo, co = py(b, max_trials=64, alpha0=a0, shrink=sh, stats=st)
+        assert st["trials"] == trc[b], (b, st, trc[b])
+        assert st["alpha"] == _repeated_product(a0, sh, st["trials"]), (b, st)
+        assert rel(xc[b], xo) < 1e-12 and rel(uc[b], uo) < 1e-12 and abs(cc[b] - co) <= 1e-12 * abs(co), b
+        seen.add(int(trc[b]))
+    assert len(seen) >= 4 and max(seen) > 4, seen
+    differ = 0
+    for j in sorted(seen):
+        aj = _repeated_product(a0, sh, j)
+        differ += aj != a0 * sh ** (j - 1)
+        x1, u1, c1, tr1 = c(alpha0=aj, shrink=sh, max_trials=1, prev_cost=np.inf)
+        at = trc == j
+        assert (tr1[at] == 1).all()   # (an overshooting trajectory's early trials may cost NaN)
+        assert np.array_equal(x1[at], xc[at]) and np.array_equal(u1[at], uc[at]) and np.array_equal(c1[at], cc[at]), j
+    assert differ > 0   # the product and the power disagree somewhere: the cases tell them apart
+
+
+def test_oracle_fits_take_the_search_options():
+    """alpha0 and shrink reach the fits: the C LQ and 2-link fits and the numpy fit at
+    (0.9, 0.7) agree on iteration and trial counts, and differ from the default fit."""
+    lq, x, u = random_lq_batch(3, 12, 4, 9, seed=2)
+    xo, uo, co, it, st = cref.lq_fit(lq, x, u, max_iter=4, tol=-1.0, mu=0.05, symmetrize=True, alpha0=0.9, shrink=0.7)
+    xd, ud, _, _, _ = cref.lq_fit(lq, x, u, max_iter=4, tol=-1.0, mu=0.05, symmetrize=True)
+    assert not np.array_equal(uo, ud)
+    for b in range(3):
+        h = []
+        xp, up = O.fit(x[b], u[b], *O.lq_closures(lq.A[b], lq.B[b], lq.Q[b], lq.R[b], lq.Qf[b]), max_iter=4,
+                       tol=-1.0, mu=0.05, symmetrize=True, max_trials=64, history=h, alpha0=0.9, shrink=0.7)
+        assert len(h) == it[b] and rel(up, uo[b]) < 1e-9
+        for e in h:
+            assert e["alpha"] == _repeated_product(0.9, 0.7, e["trials"])
+    g = np.load(os.path.join(GOLD, "twolink_t50.npz"), allow_pickle=False)
+    r = cref.tl_fit(g["x"], g["u"], max_iter=3, tol=-1.0, symmetrize=True, history=True, alpha0=0.9, shrink=0.7)
+    TL = O.TwoLink
+    for b in range(g["u"].shape[0]):
+        h = []
+        xp, up = O.fit(g["x"][b], g["u"][b], TL.dynamicsf, TL.immediate_cost, TL.final_cost, max_iter=3, tol=-1.0,
+                       symmetrize=True, max_trials=64, history=h, alpha0=0.9, shrink=0.7)
+        assert [e["trials"] for e in h] == r[5]["trials"][:, b].tolist() and rel(up, r[1][b]) < 1e-9
+
+
+def test_option_sets_tell_the_products_apart():
+    """The premise of tests/test_gpu_options.py: at (0.9, 0.7) and (1.5, 0.6) the repeated product
+    differs from alpha0·shrink^k and from its own rounding through float in most of 41 trials, and at
+    the defaults in none."""
+    for (a0, sh), least in (((0.9, 0.7), 20), ((1.5, 0.6), 20), ((1.0, 0.5), 0)):
+        rp = np.array([_repeated_product(a0, sh, j) for j in range(1, 42)])
+        n_pow = int((rp != np.array([a0 * sh ** (j - 1) for j in range(1, 42)])).sum())
+        n_f32 = int((rp != rp.astype(np.float32).astype(np.float64)).sum())
+        assert (n_pow >= least and n_f32 >= least) if least else (n_pow == 0 and n_f32 == 0), (a0, sh, n_pow, n_f32)

@@ -24,6 +24,11 @@ int oracle_lq_fit(int Bn, int T, int n, int m, const double* A, const double* Bm
                   const double* Qf, const double* x_init, const double* u_init, const double* xtraj, int max_iter,
                   double tol, double mu, int sym, int max_trials, double* x_out, double* u_out, double* cost,
                   int* iters, int* status, int nthreads);
+int oracle_lq_fit_opt(int Bn, int T, int n, int m, const double* A, const double* Bm, const double* Q, const double* R,
+                      const double* Qf, const double* x_init, const double* u_init, const double* xtraj, int max_iter,
+                      double tol, double mu, int sym, int max_trials, double alpha0, double shrink, double* x_out,
+                      double* u_out, double* cost, int* iters, int* status, int nthreads, double* hcost, int* htrials,
+                      double* hdu2, double* hgap);
 int oracle_tl_fit(int Bn, int T, int nu, const double* x_init, const double* u_init, const double* xtraj,
                   int max_iter, double tol, double mu, int sym, int max_trials, double* x_out, double* u_out,
                   double* cost, int* iters, int* status, int nthreads, double* hcost, int* htrials,
@@ -76,6 +81,14 @@ static void lq_case(int Bn, int T, int n, int m, int nthreads) {
   x[(size_t)T * n + 3] = 0.25;
   oracle_lq_fit(Bn, T, n, m, A, Bm, Q, R, Qf, x, u, NULL, 6, 1e-9, 0.01, 1, 64, xn, un, cost, it, st, nthreads);
   for (int b = 0; b < Bn; ++b) CHECK(isfinite(cost[b]) && it[b] >= 1 && it[b] <= 6, "lq_fit b=%d", b);
+  { /* the same fit off the default search options, with its per-iteration record */
+    double *hc = vec((size_t)Bn * 6, 0, 0), *hd = vec((size_t)Bn * 6, 0, 0), *hg = vec((size_t)Bn * 6, 0, 0);
+    int* ht = (int*)calloc((size_t)Bn * 6, sizeof(int));
+    oracle_lq_fit_opt(Bn, T, n, m, A, Bm, Q, R, Qf, x, u, NULL, 6, 1e-9, 0.05, 1, 64, 0.9, 0.7, xn, un, cost, it, st,
+                      nthreads, hc, ht, hd, hg);
+    for (int b = 0; b < Bn; ++b) CHECK(isfinite(cost[b]) && ht[b * 6] >= 1 && hg[b * 6] > 0, "lq_fit_opt b=%d", b);
+    free(hc); free(hd); free(hg); free(ht);
+  }
   /* tiles backward on the LQ problem's own derivatives */
   double *lx = vec((size_t)Bn * T * n, -1, 1), *lu = vec((size_t)Bn * T * m, -1, 1);
   double *lxx = vec((size_t)Bn * T * n * n, 0, 0), *luu = vec((size_t)Bn * T * m * m, 0, 0);
