@@ -1,4 +1,5 @@
-// The fit driver the LQ family (ilqr_abi.cpp) and the chain family (ilqr_chain.hip) share
+// The fit driver the LQ family (ilqr_abi.cpp), the chain family (ilqr_chain.hip) and the
+// floating-base family (ilqr_floating.hip) share
 // (src/forward_pass.jl:148-179, DESIGN.md §4 fit driver). Host code only. A handle holds one
 // FitState; a fit call fills a FitCall and runs
 //

@@ -16,8 +16,9 @@
 //     trial stores its x̄, ū as it rolls out (trial 1 into x̄, ū, the others into a
 //     per-lane slot), so an accepted later trial is taken from its slot, never rolled
 //     out again;
-//   * fb_update_kernel / fb_take_kernel: fit's bookkeeping (:161-178) and the accepted
-//     trial's move into the iterate.
+//   * fb_update_kernel / fb_take_kernel: fit's bookkeeping (:161-178) and a later
+//     accepted trial's move from its slot into the iterate; the loop around them is the
+//     shared fit driver's (ilqr_fit.h).
 //
 // Dynamics (RigidBodyDynamics.jl is absent; restated with Featherstone's algorithms in
 // body coordinates, angular first, as tests/closures.py rbd_floating_arm): the base is a
@@ -33,6 +34,7 @@
 #include <string>
 
 #include "../../include/ilqr.h"
+#include "ilqr_fit.h"
 #include "ilqr_internal.h"
 
 namespace ilqr {
@@ -1204,53 +1206,53 @@ __global__ __launch_bounds__(64 * FB_FWD_WAVES) void fb_forward_kernel(const FbM
 
 // fit's bookkeeping for one iteration (forward_pass.jl:161-178): a trajectory whose
 // backward met a NaN stops (status NAN); an exhausted or NaN search stops; an accepted
-// one takes prev_cost = cost (:168), converges when Σ(ū − u)² ≤ tol (:171, returning the
-// iterate it started from) or moves to x̄, ū (:174-175).
+// one takes prev_cost = cost (:168), converges when Σ(ū − u)² ≤ tol (:171) or moves to
+// x̄, ū (:174-175). A trajectory that stops returns the iterate the iteration started
+// from: res_parity names its buffer (ilqr_fit.h).
 __global__ __launch_bounds__(256) void fb_update_kernel(int B, int T, int it, double tol, const int32_t* __restrict__ bst,
                                                         const int32_t* __restrict__ fst, const double* __restrict__ cost,
                                                         const double* __restrict__ du2, int32_t* __restrict__ status,
                                                         int32_t* __restrict__ iters, double* __restrict__ prev_cost,
-                                                        int32_t* __restrict__ move) {
+                                                        int32_t* __restrict__ move, int32_t* __restrict__ res_parity,
+                                                        int parity) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   move[b] = 0;
   if (status[b] != ILQR_TRAJ_OK) return;
   if (bst[b] == ILQR_TRAJ_NAN) {
     status[b] = ILQR_TRAJ_NAN;
+    res_parity[b] = parity;
     return;
   }
   iters[b] = it;
   if (fst[b] != ILQR_TRAJ_OK) {
     status[b] = fst[b];
+    res_parity[b] = parity;
     return;
   }
   prev_cost[b] = cost[b];
   if (tol >= 0.0 && du2[b] <= tol) {
     status[b] = ILQR_TRAJ_CONVERGED;
+    res_parity[b] = parity;
     return;
   }
   move[b] = 1;
 }
 
-// the accepted trial's x̄, ū into (x, u): trial 1 from (xn, un), trial j > 1 from its
-// slot. fit (move ≠ null): the trajectories that move, into the iterate; forward_pass
-// (move = null): every accepted j > 1, into (xn, un) = (x, u) here
+// An accepted trial j > 1 from its slot into (x, u), where trial 1 stored its rollout as
+// it ran. fit (move ≠ null): the trajectories that move (a stopped one's fst and trials
+// are stale); forward_pass (move = null): every accepted search
 __global__ __launch_bounds__(256) void fb_take_kernel(int B, int T, int cand, const int32_t* __restrict__ move,
                                                       const int32_t* __restrict__ fst,
                                                       const int32_t* __restrict__ trials,
-                                                      const double* __restrict__ xn, const double* __restrict__ un,
                                                       const double* __restrict__ slots, double* __restrict__ x,
                                                       double* __restrict__ u) {
   const size_t nx = (size_t)(T + 1) * FB_NX, nu = (size_t)T * FB_NU;
   for (int b = blockIdx.y; b < B; b += gridDim.y) {
     const int j = trials[b];
-    if (move ? !move[b] : (fst[b] != ILQR_TRAJ_OK || j <= 1)) continue;
-    const double* sx = xn + (size_t)b * nx;
-    const double* su = un + (size_t)b * nu;
-    if (j > 1) {
-      sx = slots + ((size_t)b * cand + (j - 1) % cand) * (nx + nu);
-      su = sx + nx;
-    }
+    if ((move ? !move[b] : fst[b] != ILQR_TRAJ_OK) || j <= 1) continue;
+    const double* sx = slots + ((size_t)b * cand + (j - 1) % cand) * (nx + nu);
+    const double* su = sx + nx;
     for (size_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nx + nu; i += (size_t)gridDim.x * blockDim.x) {
       if (i < nx)
         x[(size_t)b * nx + i] = sx[i];
@@ -1258,14 +1260,6 @@ __global__ __launch_bounds__(256) void fb_take_kernel(int B, int T, int cand, co
         u[(size_t)b * nu + (i - nx)] = su[i - nx];
     }
   }
-}
-
-__global__ void fb_finish_kernel(int B, int32_t* __restrict__ status, int32_t* __restrict__ flags) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  if (status[b] == ILQR_TRAJ_OK) status[b] = ILQR_TRAJ_MAX_ITER;
-  if (status[b] == ILQR_TRAJ_NAN) atomicOr(flags, 1);
-  if (status[b] == ILQR_TRAJ_LS_EXHAUSTED) atomicOr(flags, 2);
 }
 
 }  // namespace
@@ -1279,13 +1273,13 @@ struct ilqr_floating_handle {
   ilqr::FbModel model{};
   ilqr::FbModel* model_dev = nullptr;
   hipStream_t stream = nullptr;
-  double *x = nullptr, *u = nullptr, *xn = nullptr, *un = nullptr;
+  double *xbuf[2] = {nullptr, nullptr}, *ubuf[2] = {nullptr, nullptr};  // fit's ping-pong iterates
   double *d = nullptr, *K = nullptr;
   double *A = nullptr, *Bm = nullptr, *lx = nullptr, *lu = nullptr, *lxx = nullptr, *luu = nullptr;
   double *lfx = nullptr, *lfxx = nullptr;
-  double *prev_cost = nullptr, *cost = nullptr, *du2 = nullptr;
-  int32_t *trials = nullptr, *status = nullptr, *fstatus = nullptr, *bstatus = nullptr;
-  int32_t *iters = nullptr, *move = nullptr, *words = nullptr;
+  double* cost = nullptr;  // fit's forward writes a rejected or NaN cost too: never onto fit.prev_cost
+  int32_t *fstatus = nullptr, *bstatus = nullptr, *move = nullptr;
+  ilqr::FitState fit;  // the shared fit driver's state (ilqr_fit.h), costs in fp64
   double* slots = nullptr;  // the line search's trial slots (FbFwd::slots), cand per trajectory
   int cand = 4;             // line-search lanes per trajectory (fb_cand)
 };
@@ -1380,11 +1374,11 @@ int fb_cand(int B, int T) {
 
 // fb_take_kernel over the batch: one row of blocks per trajectory, ≤ 64 blocks along it
 hipError_t fb_take(ilqr_floating_handle* h, const int32_t* move, const int32_t* fst, const int32_t* trials,
-                   const double* xn, const double* un, double* x, double* u) {
+                   double* x, double* u) {
   const size_t n = (size_t)(h->T + 1) * ilqr::FB_NX + (size_t)h->T * ilqr::FB_NU;
   const unsigned gx = (unsigned)((n + 255) / 256 < 64 ? (n + 255) / 256 : 64);
   ilqr::fb_take_kernel<<<dim3(gx, (unsigned)(h->batch < 65535 ? h->batch : 65535)), 256, 0, h->stream>>>(
-      h->batch, h->T, h->cand, move, fst, trials, xn, un, h->slots, x, u);
+      h->batch, h->T, h->cand, move, fst, trials, h->slots, x, u);
   return hipGetLastError();
 }
 
@@ -1442,10 +1436,10 @@ ilqr_status ilqr_floating_create(ilqr_floating_handle** out, int device, const i
   auto alloc = [&](auto** p, size_t bytes) {
     if (e == hipSuccess) e = hipMalloc((void**)p, bytes);
   };
-  alloc(&h->x, 8 * B * (T + 1) * nx);
-  alloc(&h->u, 8 * P * nu);
-  alloc(&h->xn, 8 * B * (T + 1) * nx);
-  alloc(&h->un, 8 * P * nu);
+  for (int i = 0; i < 2; ++i) {
+    alloc(&h->xbuf[i], 8 * B * (T + 1) * nx);
+    alloc(&h->ubuf[i], 8 * P * nu);
+  }
   alloc(&h->d, 8 * P * nu);
   alloc(&h->K, 8 * P * nu * nx);
   alloc(&h->A, 8 * P * nx * nx);
@@ -1456,16 +1450,11 @@ ilqr_status ilqr_floating_create(ilqr_floating_handle** out, int device, const i
   alloc(&h->luu, 8 * P * nu * nu);
   alloc(&h->lfx, 8 * B * nx);
   alloc(&h->lfxx, 8 * B * nx * nx);
-  alloc(&h->prev_cost, 8 * B);
   alloc(&h->cost, 8 * B);
-  alloc(&h->du2, 8 * B);
-  alloc(&h->trials, 4 * B);
-  alloc(&h->status, 4 * B);
   alloc(&h->fstatus, 4 * B);
   alloc(&h->bstatus, 4 * B);
-  alloc(&h->iters, 4 * B);
   alloc(&h->move, 4 * B);
-  alloc(&h->words, 4 * 4);
+  if (e == hipSuccess) e = ilqr::fit_state_create(&h->fit, B, 8);
   h->cand = fb_cand(batch, T);
   alloc(&h->slots, 8 * B * h->cand * ((T + 1) * nx + (size_t)T * nu));
   alloc(&h->model_dev, sizeof(ilqr::FbModel));
@@ -1481,10 +1470,11 @@ ilqr_status ilqr_floating_create(ilqr_floating_handle** out, int device, const i
 ilqr_status ilqr_floating_destroy(ilqr_floating_handle* h) {
   if (!h) return ILQR_OK;
   (void)hipSetDevice(h->device);
-  for (double* p : {h->x, h->u, h->xn, h->un, h->d, h->K, h->A, h->Bm, h->lx, h->lu, h->lxx, h->luu, h->lfx,
-                    h->lfxx, h->prev_cost, h->cost, h->du2, h->slots})
+  for (double* p : {h->xbuf[0], h->ubuf[0], h->xbuf[1], h->ubuf[1], h->d, h->K, h->A, h->Bm, h->lx, h->lu, h->lxx,
+                    h->luu, h->lfx, h->lfxx, h->cost, h->slots})
     (void)hipFree(p);
-  for (int32_t* p : {h->trials, h->status, h->fstatus, h->bstatus, h->iters, h->move, h->words}) (void)hipFree(p);
+  for (int32_t* p : {h->fstatus, h->bstatus, h->move}) (void)hipFree(p);
+  ilqr::fit_state_destroy(&h->fit);
   (void)hipFree(h->model_dev);
   delete h;
   return ILQR_OK;
@@ -1557,8 +1547,8 @@ ilqr_status ilqr_floating_forward(ilqr_floating_handle* h, const ilqr_options* o
   fa.xn = x_new;
   fa.un = u_new;
   fa.new_cost = new_cost;
-  fa.du2 = h->du2;
-  fa.trials = trials ? trials : h->trials;
+  fa.du2 = (double*)h->fit.du2;
+  fa.trials = trials ? trials : h->fit.trials;
   fa.fstatus = status ? status : h->fstatus;
   fa.status = nullptr;
   fa.slots = h->slots;
@@ -1569,7 +1559,7 @@ ilqr_status ilqr_floating_forward(ilqr_floating_handle* h, const ilqr_options* o
   // x̄, ū of a trajectory whose first trial was accepted are written as it rolled out; a
   // later accepted trial is taken from its slot; a search that accepted nothing returns
   // x, u (the closure path's rollout_forward does the same)
-  FB_TRY(fb_take(h, nullptr, fa.fstatus, fa.trials, x_new, u_new, x_new, u_new));
+  FB_TRY(fb_take(h, nullptr, fa.fstatus, fa.trials, x_new, u_new));
   FB_TRY(ilqr::fold_status(fa.fstatus, h->batch, h->stream, nullptr, &st));
   return st;
 }
@@ -1589,66 +1579,52 @@ ilqr_status ilqr_floating_fit_ex(ilqr_floating_handle* h, const ilqr_options* o,
   if (st != ILQR_OK) return st;
   FB_TRY(hipSetDevice(h->device));
   const ilqr::LSParams ls = ilqr::ls_params(o);
-  const int max_iter = o ? o->max_iter : 100;
+  // The shared fit driver (ilqr_fit.h, DESIGN.md §4 fit driver) around this family's iteration
   const int B = h->batch, T = h->T;
-  const size_t nxe = (size_t)(T + 1) * ilqr::FB_NX, nue = (size_t)T * ilqr::FB_NU;
   hipStream_t s = h->stream;
-  FB_TRY(hipMemcpyAsync(h->x, x_init, 8 * B * nxe, hipMemcpyDeviceToDevice, s));
-  FB_TRY(hipMemcpyAsync(h->u, u_init, 8 * B * nue, hipMemcpyDeviceToDevice, s));
-  FB_TRY(ilqr::launch_fill_f64(h->prev_cost, B, INFINITY, s));  // :159
-  FB_TRY(ilqr::launch_fill_i32(h->status, B, ILQR_TRAJ_OK, s));
-  FB_TRY(ilqr::launch_fill_i32(h->iters, B, 0, s));
-  FB_TRY(hipMemsetAsync(h->words, 0, 4 * 4, s));
+  ilqr::FitState& f = h->fit;
+  ilqr::FitCall c;
+  c.B = B, c.T = T, c.nx = ilqr::FB_NX, c.nu = ilqr::FB_NU;
+  c.max_iter = o ? o->max_iter : 100;
+  c.x_init = x_init, c.u_init = u_init, c.x_out = x_out, c.u_out = u_out;
+  for (int i = 0; i < 2; ++i) c.xbuf[i] = h->xbuf[i], c.ubuf[i] = h->ubuf[i];
+  FB_TRY(ilqr::fit_begin(f, c, x_traj, ls.tol, /*init=*/true, s));
   const ilqr::TileParams tp{h->A, h->Bm, h->lx, h->lu, h->lxx, nullptr, h->luu, h->lfx, h->lfxx};
   ilqr::FbFwd fa{};
-  fa.x = h->x;
-  fa.u = h->u;
   fa.xtraj = x_traj;
   fa.d = h->d;
   fa.K = h->K;
-  fa.prev_cost = h->prev_cost;
-  fa.xn = h->xn;
-  fa.un = h->un;
+  fa.prev_cost = (const double*)f.prev_cost;
   fa.new_cost = h->cost;
-  fa.du2 = h->du2;
-  fa.trials = h->trials;
+  fa.du2 = (double*)f.du2;
+  fa.trials = f.trials;
   fa.fstatus = h->fstatus;
-  fa.status = h->status;
+  fa.status = f.status;
   fa.slots = h->slots;
   fa.alpha0 = ls.alpha0;
   fa.shrink = ls.shrink;
   fa.max_trials = ls.max_trials;
-  const unsigned g = (unsigned)((B + 255) / 256);
-  for (int it = 1; it <= max_iter; ++it) {  // forward_pass.jl:161
-    FB_TRY(fb_linearize(h, h->x, h->u, h->status));
+  for (int it = 1; it <= c.max_iter; ++it) {  // forward_pass.jl:161
+    const ilqr::FitBuffers b = ilqr::fit_buffers(c, it);
+    fa.x = (const double*)b.x, fa.u = (const double*)b.u;
+    fa.xn = (double*)b.xnew, fa.un = (double*)b.unew;  // trial 1 rolls out into the next iterate
+    FB_TRY(fb_linearize(h, fa.x, fa.u, f.status));
     FB_TRY(ilqr::launch_tiles_backward(ilqr::FB_NX, ilqr::FB_NU, tp, B, T, h->d, h->K, h->bstatus, ls.mu, s));
     FB_TRY(fb_forward(h, fa));
-    ilqr::fb_update_kernel<<<g, 256, 0, s>>>(B, T, it, ls.tol, h->bstatus, h->fstatus, h->cost, h->du2,
-                                             h->status, h->iters, h->prev_cost, h->move);
+    ilqr::fb_update_kernel<<<(unsigned)((B + 255) / 256), 256, 0, s>>>(
+        B, T, it, ls.tol, h->bstatus, h->fstatus, h->cost, fa.du2, f.status, f.iters, (double*)f.prev_cost, h->move,
+        f.res_parity, b.parity);
     FB_TRY(hipGetLastError());
-    FB_TRY(fb_take(h, h->move, h->fstatus, h->trials, h->xn, h->un, h->x, h->u));
+    FB_TRY(fb_take(h, h->move, h->fstatus, f.trials, fa.xn, fa.un));
     if (hist)  // the per-iteration record (ilqr_history), as the other families'
-      FB_TRY(ilqr::launch_record_history(B, it, h->status, h->iters, h->trials, h->prev_cost, h->du2, false,
-                                         ls.alpha0, ls.shrink, hist->cost, hist->trials, hist->alpha, hist->du2, s));
-    if (ls.tol >= 0.0 && it < max_iter) {  // :171's break once every trajectory stopped
-      FB_TRY(ilqr::launch_count_running(B, h->status, h->words, s));
-      int32_t running = 0;
-      FB_TRY(hipMemcpyAsync(&running, h->words, 4, hipMemcpyDeviceToHost, s));
-      FB_TRY(hipStreamSynchronize(s));
-      if (running == 0) break;
-    }
+      FB_TRY(ilqr::launch_record_history(B, it, f.status, f.iters, f.trials, f.prev_cost, f.du2, false, ls.alpha0,
+                                         ls.shrink, hist->cost, hist->trials, hist->alpha, hist->du2, s));
+    bool stopped;
+    FB_TRY(ilqr::fit_poll(f, c, it, s, &stopped));
+    if (stopped) break;
   }
-  ilqr::fb_finish_kernel<<<g, 256, 0, s>>>(B, h->status, h->words + 1);
-  FB_TRY(hipGetLastError());
-  FB_TRY(hipMemcpyAsync(x_out, h->x, 8 * B * nxe, hipMemcpyDeviceToDevice, s));
-  FB_TRY(hipMemcpyAsync(u_out, h->u, 8 * B * nue, hipMemcpyDeviceToDevice, s));
-  if (cost) FB_TRY(hipMemcpyAsync(cost, h->prev_cost, 8 * B, hipMemcpyDeviceToDevice, s));
-  if (iters) FB_TRY(hipMemcpyAsync(iters, h->iters, 4 * B, hipMemcpyDeviceToDevice, s));
-  if (status) FB_TRY(hipMemcpyAsync(status, h->status, 4 * B, hipMemcpyDeviceToDevice, s));
-  int32_t flags = 0;
-  FB_TRY(hipMemcpyAsync(&flags, h->words + 1, 4, hipMemcpyDeviceToHost, s));
-  FB_TRY(hipStreamSynchronize(s));
-  return ilqr::call_status(flags);
+  FB_TRY(ilqr::fit_end(f, c, cost, iters, status, s, &st));
+  return st;
 }
 
 }  // extern "C"

@@ -278,6 +278,180 @@ def test_floating_fit_x_traj_and_edges(gpu):
     assert r0.status.tolist() == [_lib.TRAJ_MAX_ITER] * nb and r0.iters.tolist() == [0] * nb
 
 
+def floating_fit_replay(s, x0, u0, o, x_traj=None):
+    """fit (forward_pass.jl:148-179) restated as ilqr_floating_backward / _forward calls with
+    fit's bookkeeping here: prev_cost = Inf, each iteration on the still-running
+    trajectories (the forward's outputs of the others are ignored), a NaN backward stops a
+    trajectory before its iteration count is set, a trajectory that stops keeps the
+    iteration's INPUT (converged: the pre-update iterate, :171; NaN / exhausted search: the
+    last accepted one), the running ones the last accepted iterate and MAX_ITER.
+    ilqr_floating_forward does not return Σ(ū − u)²: formed here, in fp64 (the caller keeps
+    tol away from every such sum)."""
+    nb = x0.shape[0]
+    x, u = x0.clone(), u0.clone()
+    pc = torch.full((nb,), float("inf"), dtype=torch.float64, device="cuda")
+    st = torch.zeros((nb,), dtype=torch.int32, device="cuda")
+    it_out = torch.zeros((nb,), dtype=torch.int32, device="cuda")
+    rx, ru = x0.clone(), u0.clone()
+    for it in range(1, o.max_iter + 1):
+        run = st == 0
+        if not bool(run.any()):
+            break
+        d, K, bst = s.backward(x, u, options=o)
+        nanb = run & (bst == _lib.TRAJ_NAN)
+        live = run & ~nanb
+        xn, un, cost, _, fst = s.forward(x, u, d, K, pc, x_traj=x_traj, options=o)
+        it_out[live] = it
+        acc = live & (fst == _lib.TRAJ_OK)
+        pc = torch.where(acc, cost, pc)                                     # :168
+        conv = acc & (((un - u) ** 2).sum(dim=(1, 2)) <= o.tol) if o.tol >= 0 else torch.zeros_like(acc)
+        st = torch.where(nanb, torch.full_like(st, _lib.TRAJ_NAN), st)
+        st = torch.where(live & ~acc, fst, st)
+        st = torch.where(conv, torch.full_like(st, _lib.TRAJ_CONVERGED), st)
+        stopped = run & (st != 0)
+        rx[stopped], ru[stopped] = x[stopped], u[stopped]
+        keep = (acc & ~conv)[:, None, None]
+        x, u = torch.where(keep, xn, x), torch.where(keep, un, u)          # :174-175
+    run = st == 0
+    rx[run], ru[run] = x[run], u[run]
+    st = torch.where(run, torch.full_like(st, _lib.TRAJ_MAX_ITER), st)
+    s_np = st.cpu().numpy()
+    cs = _lib.ERR_NAN if (s_np == _lib.TRAJ_NAN).any() else (
+        _lib.ERR_LS_EXHAUSTED if (s_np == _lib.TRAJ_LS_EXHAUSTED).any() else _lib.OK)
+    return rx, ru, pc, it_out, st, cs
+
+
+def floating_fit_call(s, o, x_init, u_init, x_traj, x_out, u_out):
+    """ilqr_floating_fit_ex on the caller's own buffers (FloatingSolver.fit always allocates
+    fresh outputs) → (x, u, cost, iters, status, call status), history."""
+    import ctypes as C
+    from ilqr_amd.solver import alloc_history
+    nb = x_init.shape[0]
+    cost = torch.empty((nb,), dtype=torch.float64, device="cuda")
+    it = torch.empty((nb,), dtype=torch.int32, device="cuda")
+    st = torch.empty((nb,), dtype=torch.int32, device="cuda")
+    hist, hst = alloc_history(o.max_iter, nb, x_init.device)
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    s._bind()
+    cs = s.lib.ilqr_floating_fit_ex(s.h, C.byref(o), p(x_init), p(u_init), p(x_traj), p(x_out), p(u_out), p(cost),
+                                    p(it), p(st), C.byref(hst))
+    return (x_out, u_out, cost, it, st, cs), hist
+
+
+def accepted_later_trial(hist, above=1):
+    """some trajectory accepted a trial j > above in some iteration (an accepted search's
+    cost is recorded, a failed one's is NaN)"""
+    return bool(((hist["trials"] > above) & torch.isfinite(hist["cost"])).any())
+
+
+# The line search of the fit cases below. With the script's weights every trajectory of
+# fit_inputs accepts a step up to α ≈ 2.01 in iteration 2 (2.0111 for trajectory 3, 2.0124 to
+# 2.0135 for the others, by the closure oracle): α₀ between them makes trajectory 3 take
+# trial 2 there (α = 0.4·α₀, its Σ(ū − u)² about 0.4⁻² = 6 times smaller) and the others
+# trial 1, and the later iterations alternate between trials 1 and 2.
+FIT_ALPHA0, FIT_SHRINK = 2.0118, 0.4
+
+
+@pytest.fixture(scope="module")
+def fit_inputs():
+    """T = 6, B = 5: script_batch plus the input noise of
+    test_floating_forward_slots_rounds_and_partial_workgroups, x the rollout of u."""
+    nb, T = 5, 6
+    x, u = script_batch(nb, T, seed=29)
+    u = u + 0.5 * np.random.default_rng(31).standard_normal(u.shape)
+    fj, _, _ = rbd_floating_arm(jet_ns())
+    for t in range(T):
+        x[:, t + 1] = fj(x[:, t], u[:, t])
+    return x, u
+
+
+@pytest.fixture(scope="module")
+def fit_tol(gpu, fit_inputs):
+    """The tol of the 'some converge early' case, from a tol = −1 run's Σ(ū − u)² history: the
+    geometric mean of the two adjacent sorted iteration-2 values with the largest ratio,
+    which must be ≥ 4; and no recorded value of any (iteration, trajectory) within
+    [tol / 2, 2·tol], so the replay's torch sum decides every `≤ tol` as the device's does."""
+    x, u = fit_inputs
+    s = FloatingSolver(rbd_example_problem(), x.shape[1] - 1, x.shape[0])
+    try:
+        r = s.fit(torch.from_numpy(x).cuda(), torch.from_numpy(u).cuda(), history=True,
+                  options=_lib.default_options(max_iter=6, tol=-1.0, alpha0=FIT_ALPHA0, shrink=FIT_SHRINK))
+    finally:
+        s.close()
+    assert accepted_later_trial(r.history)
+    du2 = r.history["du2"].cpu().numpy()
+    v = np.sort(du2[1])
+    k = int(np.argmax(v[1:] / v[:-1]))
+    print("iteration-2 du2", v, "ratio", v[k + 1] / v[k])
+    assert v[k + 1] / v[k] >= 4.0
+    tol = float(np.sqrt(v[k] * v[k + 1]))
+    assert np.isfinite(du2).all() and not ((du2 >= tol / 2) & (du2 <= 2 * tol)).any(), (tol, du2)
+    return tol
+
+
+@pytest.mark.parametrize("max_iter,tol,extra", [
+    (20, 1e30, None),      # every trajectory converges in iteration 1: the poll ends the loop,
+                           # the result is the input
+    (6, "gap", None),      # some converge in iteration 2, the others later (fit_tol)
+    (6, -1.0, "nan"),      # max_trials = 2: exhausted searches, and a NaN state in trajectory 1
+    (5, -1.0, "inplace"),  # x_out = x_init, u_out = u_init: no direct output, the gather copies
+    (4, -1.0, "xtraj"),    # x_out = x_traj: read by every iteration, written only by the gather
+    (1, -1.0, None),       # a single iteration
+    (0, -1.0, None),       # the input is the result
+    (3, -1.0, "cand4"),    # 4 lanes a trajectory and accepted trials j > 4: taken from a wrapped
+                           # slot (j − 1) mod 4 into the ping-pong buffer
+])
+def test_floating_fit_equals_backward_forward_replay(gpu, fit_inputs, request, monkeypatch, max_iter, tol, extra):
+    """The floating fit on the shared fit driver (iteration 1 on the caller's x_init in place,
+    trial 1 rolled out straight into the next ping-pong buffer and the last iteration's into
+    x_out, later trials taken from their slots, the running-count poll, one gather + the
+    published call status) returns exactly what the same iterations through
+    ilqr_floating_backward / _forward do: x, u, cost, iterations, status and call status, bit
+    for bit; twice on one handle (the re-armed call-status word). Every case whose search
+    compares costs (prev_cost is +Inf in iteration 1, where trial 1 is always the accepted
+    one) accepts some trial j > 1, by its history."""
+    if tol == "gap":
+        tol = request.getfixturevalue("fit_tol")
+    x, u = fit_inputs
+    x0, u0 = torch.from_numpy(x).cuda(), torch.from_numpy(u).cuda()
+    o = _lib.default_options(max_iter=max_iter, tol=tol, alpha0=FIT_ALPHA0, shrink=FIT_SHRINK)
+    if extra == "nan":
+        x0[1, 3, 2] = float("nan")
+        o.max_trials, o.alpha0 = 2, FIT_ALPHA0 / FIT_SHRINK  # trial 2 at the α that splits the batch
+    if extra == "cand4":
+        monkeypatch.setenv("ILQR_FB_CAND", "4")  # the lanes a trajectory, read at creation
+        o.alpha0, o.shrink = 40.0, 0.6           # α ≤ 2 from trial 7 on
+    xt0 = x0.flip(1).contiguous() if extra == "xtraj" else None  # other states as the target
+    s = FloatingSolver(rbd_example_problem(), x.shape[1] - 1, x.shape[0])
+    try:
+        ref = floating_fit_replay(s, x0, u0, o, x_traj=xt0)
+        for _ in range(2):
+            xi, ui = x0.clone(), u0.clone()
+            xt = None if xt0 is None else xt0.clone()
+            if extra == "inplace":
+                xo, uo = xi, ui
+            else:
+                xo, uo = (xt if extra == "xtraj" else torch.empty_like(xi)), torch.empty_like(ui)
+            got, hist = floating_fit_call(s, o, xi, ui, xt, xo, uo)
+            assert got[5] == ref[5]
+            for a, b in zip(got[:4], ref[:4]):
+                torch.testing.assert_close(a, b, rtol=0, atol=0, equal_nan=True)
+            assert torch.equal(got[4], ref[4])
+            if max_iter >= 3 and tol < 1e30:
+                assert accepted_later_trial(hist, above=4 if extra == "cand4" else 1)
+    finally:
+        s.close()
+    if max_iter == 20:
+        assert ref[4].tolist() == [_lib.TRAJ_CONVERGED] * 5 and ref[3].tolist() == [1] * 5
+        assert torch.equal(ref[0], x0) and torch.equal(ref[1], u0)
+    if tol not in (-1.0, 1e30):
+        conv = sorted(ref[3][ref[4] == _lib.TRAJ_CONVERGED].tolist())
+        assert conv and conv[0] == 2 and (conv[-1] > 2 or len(conv) < 5)  # early, and not
+    if extra == "nan":
+        assert ref[4][1].item() == _lib.TRAJ_NAN and ref[3][1].item() == 0 and ref[5] == _lib.ERR_NAN
+        assert (ref[4] == _lib.TRAJ_LS_EXHAUSTED).any()
+
+
 def _problem_of(model):
     from ilqr_amd.floating import FloatingProblem
     from ilqr_amd.urdf import Chain

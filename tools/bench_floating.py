@@ -3,9 +3,13 @@ ilqr_floating_*): test/RBD_2_link_example/animate_RBD_2_link.jl's problem, nx = 
 nu = 8, T = 1000, from its own start (rest state, zero inputs, x_init = rollout).
 Prints one JSON line per batch size: ms per fit iteration (a fit of `iters` iterations
 with the convergence test disabled, median of `reps` after a warm-up), beside the
-generic closure path's per-iteration cost (profiles/r05/rbd_fit_breakdown_r05.json).
+generic closure path's per-iteration cost (profiles/r05/rbd_fit_breakdown_r05.json),
+and the host CPU time of a fit (time.process_time around the call). --converge[=TOL]:
+the fit with the convergence test on instead (max_iter = 100; tol = 1e-6 as the script
+calls it, which 100 iterations from this start do not reach; --converge=1e30 stops every
+trajectory in iteration 1), its wall time and iteration count.
 
-    PYTHONPATH=.:ilqr.jl_amd python tools/bench_floating.py [iters] [reps] [B ...]
+    PYTHONPATH=.:ilqr.jl_amd python tools/bench_floating.py [--converge[=TOL]] [iters] [reps] [B ...]
 """
 import json
 import os
@@ -24,7 +28,7 @@ from ilqr_amd import _lib  # noqa: E402
 from ilqr_amd.floating import FloatingSolver, rbd_example_problem, rbd_initial_state  # noqa: E402
 
 
-def measure(nb, T=1000, iters=5, reps=3):
+def measure(nb, T=1000, iters=5, reps=3, converge=None):
     p = rbd_example_problem()
     s = FloatingSolver(p, T, nb)
     try:
@@ -32,20 +36,23 @@ def measure(nb, T=1000, iters=5, reps=3):
         x0[1:, 8:] = 0.05 * np.random.default_rng(7).standard_normal((nb - 1, 8))
         u = torch.zeros(nb, T, 8, dtype=torch.float64, device="cuda")
         x = s.rollout(torch.from_numpy(x0).cuda(), u)
-        o = _lib.default_options(max_iter=iters, tol=-1.0)
+        o = _lib.default_options(max_iter=iters, tol=-1.0) if converge is None else _lib.default_options(max_iter=100, tol=converge)
         r = s.fit(x, u, options=o)  # warm-up
-        times = []
+        times, cpu = [], []
         for _ in range(reps):
             torch.cuda.synchronize()
-            t0 = time.perf_counter()
+            t0, c0 = time.perf_counter(), time.process_time()
             r = s.fit(x, u, options=o)
             torch.cuda.synchronize()
             times.append((time.perf_counter() - t0) * 1e3)
+            cpu.append((time.process_time() - c0) * 1e3)
         st = r.status.cpu().numpy()
+        iters = int(r.iters.max())  # == the options' without the convergence test
         return {"workload": "animate_RBD_2_link.jl fit (floating 2Dof_arm, native)", "nx": 16, "nu": 8,
                 "T": T, "B": nb, "iters": iters, "ms_per_fit": float(np.median(times)),
                 "ms_per_iteration": float(np.median(times)) / iters,
                 "batched_it_per_s": 1e3 * iters / float(np.median(times)),
+                "host_cpu_ms_per_fit": float(np.median(cpu)), "converge": converge,
                 "status_counts": {int(k): int(v) for k, v in zip(*np.unique(st, return_counts=True))},
                 "cost0": float(r.cost[0])}
     finally:
@@ -53,11 +60,13 @@ def measure(nb, T=1000, iters=5, reps=3):
 
 
 def main():
-    iters = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
-    batches = [int(v) for v in sys.argv[3:]] or [1, 256]
+    argv = [a for a in sys.argv[1:] if not a.startswith("--converge")]
+    conv = [float(a.partition("=")[2] or 1e-6) for a in sys.argv[1:] if a.startswith("--converge")]
+    iters = int(argv[0]) if len(argv) > 0 else 5
+    reps = int(argv[1]) if len(argv) > 1 else 3
+    batches = [int(v) for v in argv[2:]] or [1, 256]
     for nb in batches:
-        print(json.dumps(measure(nb, iters=iters, reps=reps)), flush=True)
+        print(json.dumps(measure(nb, iters=iters, reps=reps, converge=conv[0] if conv else None)), flush=True)
 
 
 if __name__ == "__main__":
