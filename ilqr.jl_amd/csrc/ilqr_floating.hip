@@ -7,7 +7,10 @@
 //     one lane per (point, input direction), the RK4 step in forward-mode duals
 //     (ForwardDiff's algorithm, one partial per lane: exact like ForwardDiff), plus the
 //     costs' derivative tiles (:81-109, :134-153) in closed form — the costs are
-//     diagonal weighted squares (:85-116);
+//     diagonal weighted squares (:85-116); or, on a handle set to ILQR_LINEARIZE_ANALYTIC
+//     (ilqr_floating_set_linearization), fb_analytic_primal_kernel + fb_analytic_tangent_kernel:
+//     the same exact A, B from δν̇ = M⁻¹(δu − δ[ID(θ, ν, ν̇)]), M and the solve never
+//     differentiated (the comment above fb_id);
 //   * the Riccati recursion: the wide tiles kernel (ilqr_tiles.hip, nx ≤ 16, nu ≤ 8);
 //   * fb_forward_kernel: forward_pass (forward_pass.jl:55-93) — 4 to 64 line-search
 //     trials of a trajectory at once, one per lane, each RK4 step split over the four
@@ -668,6 +671,275 @@ __global__ __launch_bounds__(256) void fb_linearize_kernel(const FbModel* __rest
   }
 }
 
+// ILQR_LINEARIZE_ANALYTIC (ilqr_floating_set_linearization): the same exact Jacobians without
+// differentiating M or the solve. With ID(θ, ν, ν̇) = M(θ)ν̇ + b(θ, ν) — the Newton-Euler pass
+// with accelerations, fb_id below; fb_bias is its ν̇ = 0 case — a stage's ν̇ = M⁻¹(u − b) gives
+//   δν̇ = M⁻¹(δu − δ[ID(θ, ν, ν̇)]),  ν̇ held fixed,
+// so a direction costs one tangent pass (fb_id<D1>: θ and ν dual, ν̇ constant), the kinematic
+// rows (fb_kin<D1>) and one solve with the stage's factors (fb_accel on the shared
+// FbSchur<double>) per RK4 stage. The stage's primal — its state y, the two sincos, the bias,
+// the CRBA, the Schur factors and ν̇ — is the same for the 21 directions of a point, and the
+// primal of stage s + 1 depends on the primals before it alone (y_{s+1} = x + a·k_s), never on a
+// tangent. So two launches:
+//   fb_analytic_primal_kernel   one lane per point: the RK4 step in doubles (fb_step's stages),
+//                               each stage's y, ν̇, sin θ, cos θ and factors (FB_AN_NS doubles)
+//                               into a scratch record of the point;
+//   fb_analytic_tangent_kernel  one lane per (point, direction), fb_linearize_kernel's lane map:
+//                               the four tangent stages reading the point's record (the 21
+//                               lanes of a point read the same words: one fetch a wave), column
+//                               dir of A or B, and the cost tiles in fb_linearize_kernel's
+//                               expressions, a row per lane (lanes 0..15 a row of lxx, and of
+//                               lfxx at the last step; lanes 13..20 a row of luu).
+// With the primal on a lane of the tangent's wave instead (a wave-private LDS region, three
+// points a wave) every wave waits its primal out, 40 % of its instructions for 3 of 64 lanes:
+// 11.60 ms at B = 1024, T = 1000 against the duals' 12.29, where the two launches take 9.60
+// (profiles/floating_analytic/).
+// The scratch is the line search's trial slots, idle while a handle linearises; the points
+// are taken in chunks of as many records as the slots hold.
+template <class S>
+__device__ __forceinline__ void fb_id(const FbModel& P, const S (&R)[FB_NJ][9], const S (&x)[FB_NX],
+                                      const double (&nd)[FB_NU], S (&q)[FB_NU]) {
+  // outward (fb_outward with a₀ = (ω̇, v̇) and the joints' s q̈):
+  // a_{i+1} = X a_i + s q̈ + v_{i+1} × (s q̇)
+  FbMotion<S> M;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    M.vw[0][k] = x[8 + k];
+    M.vv[0][k] = x[11 + k];
+    M.aw[0][k] = nd[k];
+    M.av[0][k] = nd[3 + k];
+  }
+#pragma unroll
+  for (int i = 0; i < FB_NJ; ++i) {
+    S pw[3], t[3], sw[3], c1[3], c2[3];
+    crossm(P.p[i], M.vw[i], pw);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t[k] = M.vv[i][k] - pw[k];
+    rot_t(R[i], M.vw[i], M.vw[i + 1]);
+    rot_t(R[i], t, M.vv[i + 1]);
+    const S qd = x[14 + i];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      sw[k] = P.ax[i][k] * qd;
+      M.vw[i + 1][k] = M.vw[i + 1][k] + sw[k];
+    }
+    crossm(P.p[i], M.aw[i], pw);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t[k] = M.av[i][k] - pw[k];
+    rot_t(R[i], M.aw[i], M.aw[i + 1]);
+    rot_t(R[i], t, M.av[i + 1]);
+    crossm(M.vw[i + 1], sw, c1);
+    crossm(M.vv[i + 1], sw, c2);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      M.aw[i + 1][k] = M.aw[i + 1][k] + (c1[k] + S(P.ax[i][k] * nd[6 + i]));
+      M.av[i + 1][k] = M.av[i + 1][k] + c2[k];
+    }
+  }
+  // inward, as fb_bias
+  S fn[3], ff[3], tau[FB_NJ];
+#pragma unroll
+  for (int i = FB_NJ; i >= 0; --i) {
+    S bn[3], bf[3];
+    fb_body_force(P, i, M, bn, bf);
+    if (i < FB_NJ) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        bn[k] = bn[k] + fn[k];
+        bf[k] = bf[k] + ff[k];
+      }
+    }
+    if (i > 0) {
+      fb_transmit(P, R, i, bn, bf, tau[i - 1], fn, ff);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        fn[k] = bn[k];
+        ff[k] = bf[k];
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    q[k] = fn[k];
+    q[3 + k] = ff[k];
+  }
+#pragma unroll
+  for (int j = 0; j < FB_NJ; ++j) q[6 + j] = tau[j];
+}
+
+// A stage's record: y (NX), ν̇ (NU), sin θ, cos θ (2·NJ) and the factors (FbSchur<double>)
+constexpr int FB_AN_SCHUR_N = (int)(sizeof(FbSchur<double>) / sizeof(double));
+static_assert(sizeof(FbSchur<double>) == FB_AN_SCHUR_N * sizeof(double), "FbSchur<double> is doubles only");
+constexpr int FB_AN_ND = FB_NX, FB_AN_SC = FB_NX + FB_NU, FB_AN_F = FB_AN_SC + 2 * FB_NJ;
+constexpr int FB_AN_NS = FB_AN_F + FB_AN_SCHUR_N;
+constexpr int FB_AN_NP = 4 * FB_AN_NS;  // a point's four stages
+// the stage at y, u: its record into reg and f(y, u) into xd
+__device__ __forceinline__ void fb_analytic_primal(const FbModel& P, const double (&y)[FB_NX],
+                                                   const double (&u)[FB_NU], double* __restrict__ reg,
+                                                   double (&xd)[FB_NX]) {
+  double R[FB_NJ][9];
+#pragma unroll
+  for (int i = 0; i < FB_NJ; ++i) {
+    double s, c;
+    sincos_s(y[6 + i], s, c);
+    joint_rot(P, i, c, s, R[i]);
+    reg[FB_AN_SC + i] = s;
+    reg[FB_AN_SC + FB_NJ + i] = c;
+  }
+  double b[FB_NU];
+  fb_bias(P, R, y, b);
+#pragma unroll
+  for (int k = 0; k < FB_NU; ++k) b[k] = u[k] - b[k];
+  FbSchur<double> F;
+  fb_mass(P, R, F);
+  fb_solve(F, b, y, xd);
+  const double* f = reinterpret_cast<const double*>(&F);
+#pragma unroll
+  for (int k = 0; k < FB_NX; ++k) reg[k] = y[k];
+#pragma unroll
+  for (int k = 0; k < FB_NU; ++k) reg[FB_AN_ND + k] = xd[8 + k];
+#pragma unroll
+  for (int k = 0; k < FB_AN_SCHUR_N; ++k) reg[FB_AN_F + k] = f[k];
+}
+// Direction (dy, δu = e_{du}, du < 0: none) through the stage whose record is reg: δf into dxd
+__device__ __forceinline__ void fb_analytic_tangent(const FbModel& P, const double* __restrict__ reg,
+                                                    const double (&dy)[FB_NX], int du, double (&dxd)[FB_NX]) {
+  D1 R[FB_NJ][9], xD[FB_NX], tau[FB_NU], kin[FB_NX];
+#pragma unroll
+  for (int i = 0; i < FB_NJ; ++i) {
+    const double s = reg[FB_AN_SC + i], c = reg[FB_AN_SC + FB_NJ + i];
+    joint_rot(P, i, D1(c, -s * dy[6 + i]), D1(s, c * dy[6 + i]), R[i]);
+  }
+#pragma unroll
+  for (int k = 0; k < FB_NX; ++k) xD[k] = D1(reg[k], dy[k]);
+  double nd[FB_NU];
+#pragma unroll
+  for (int k = 0; k < FB_NU; ++k) nd[k] = reg[FB_AN_ND + k];
+  fb_id(P, R, xD, nd, tau);
+  double r[FB_NU];
+#pragma unroll
+  for (int k = 0; k < FB_NU; ++k) r[k] = (k == du ? 1.0 : 0.0) - tau[k].d;
+  FbSchur<double> F;
+  double* f = reinterpret_cast<double*>(&F);
+#pragma unroll
+  for (int k = 0; k < FB_AN_SCHUR_N; ++k) f[k] = reg[FB_AN_F + k];
+  fb_accel(F, r, dxd);
+  fb_kin(xD, kin);
+#pragma unroll
+  for (int k = 0; k < FB_NQ; ++k) dxd[k] = kin[k].d;
+}
+
+// RK4's weights as fb_step takes them: y_s = x + a_s k_{s−1} with a = 0, ½, ½, 1 (k₀ = 0) and
+// the sum ((k₁ + 2k₂) + 2k₃) + k₄
+__device__ __forceinline__ double fb_an_a(int s) { return s == 0 ? 0.0 : s == 3 ? 1.0 : 0.5; }
+__device__ __forceinline__ double fb_an_w(int s) { return (s == 1 || s == 2) ? 2.0 : 1.0; }
+
+// points p0 .. p0 + n − 1 (b·T + t); record i·4 + s of `rec` is point p0 + i's stage s
+__global__ __launch_bounds__(256) void fb_analytic_primal_kernel(const FbModel* __restrict__ Pm, int T, size_t p0, size_t n,
+                                                                 const double* __restrict__ x,
+                                                                 const double* __restrict__ u,
+                                                                 const int32_t* __restrict__ status,
+                                                                 double* __restrict__ rec) {
+  const FbModel& P = *Pm;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const size_t pt = p0 + i;
+  const int b = (int)(pt / T), t = (int)(pt - (size_t)b * T);
+  if (status && status[b] != ILQR_TRAJ_OK) return;
+  const double* xp = x + ((size_t)b * (T + 1) + t) * FB_NX;
+  const double* up = u + pt * FB_NU;
+  double xs[FB_NX], us[FB_NU], kp[FB_NX];
+#pragma unroll
+  for (int k = 0; k < FB_NX; ++k) {
+    xs[k] = xp[k];
+    kp[k] = 0.0;
+  }
+#pragma unroll
+  for (int k = 0; k < FB_NU; ++k) us[k] = up[k];
+#pragma unroll 1
+  for (int s = 0; s < 4; ++s) {
+    asm volatile("" ::: "memory");  // the model's constants re-read per stage (fb_step)
+    const double a = fb_an_a(s);
+    double y[FB_NX], xd[FB_NX];
+#pragma unroll
+    for (int k = 0; k < FB_NX; ++k) y[k] = xs[k] + a * kp[k];
+    fb_analytic_primal(P, y, us, rec + (i * 4 + s) * FB_AN_NS, xd);
+#pragma unroll
+    for (int k = 0; k < FB_NX; ++k) kp[k] = P.dt * xd[k];
+  }
+}
+
+// One wave a SIMD (414 registers, no scratch): held to two, the pass spills 628 bytes a lane
+// and the launch takes 19.4 ms where it takes 8.8 (B = 1024, T = 1000). Touching a stage's
+// record a stage ahead, so that its reads hit the vector cache, gains nothing (8.94 against
+// 8.84 ms): the wave waits on its own arithmetic, not on the fetches.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void fb_analytic_tangent_kernel(
+    const FbModel* __restrict__ Pm, int T, size_t p0, size_t n, const double* __restrict__ x,
+    const double* __restrict__ u, const int32_t* __restrict__ status, const double* __restrict__ rec,
+    double* __restrict__ A, double* __restrict__ Bm, double* __restrict__ lx, double* __restrict__ lu,
+    double* __restrict__ lxx, double* __restrict__ luu, double* __restrict__ lfx, double* __restrict__ lfxx) {
+  constexpr int ND = FB_LIN_DIRS;
+  const FbModel& P = *Pm;
+  const size_t lane = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (lane >= n * ND) return;
+  const size_t i = lane / ND;
+  const int kd = (int)(lane - i * ND);
+  const int dir = kd < 3 ? kd : kd + 3;  // directions 3..5 (r) are not seeded
+  const size_t pt = p0 + i;
+  const int b = (int)(pt / T), t = (int)(pt - (size_t)b * T);
+  if (status && status[b] != ILQR_TRAJ_OK) return;
+  double dkp[FB_NX], acc[FB_NX];
+#pragma unroll
+  for (int k = 0; k < FB_NX; ++k) dkp[k] = acc[k] = 0.0;
+#pragma unroll 1
+  for (int s = 0; s < 4; ++s) {
+    asm volatile("" ::: "memory");  // the model's constants re-read per stage (fb_step)
+    const double a = fb_an_a(s), wgt = fb_an_w(s);
+    double dy[FB_NX], dxd[FB_NX];
+#pragma unroll
+    for (int k = 0; k < FB_NX; ++k) dy[k] = (k == dir ? 1.0 : 0.0) + a * dkp[k];
+    fb_analytic_tangent(P, rec + (i * 4 + s) * FB_AN_NS, dy, dir - FB_NX, dxd);
+#pragma unroll
+    for (int k = 0; k < FB_NX; ++k) {
+      dkp[k] = P.dt * dxd[k];
+      acc[k] = acc[k] + wgt * dkp[k];
+    }
+  }
+  if (dir < FB_NX) {
+#pragma unroll
+    for (int k = 0; k < FB_NX; ++k) A[(pt * FB_NX + k) * FB_NX + dir] = (k == dir ? 1.0 : 0.0) + (1.0 / 6.0) * acc[k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < FB_NX; ++k) Bm[(pt * FB_NX + k) * FB_NU + (dir - FB_NX)] = (1.0 / 6.0) * acc[k];
+  }
+  if (kd == 0) {
+#pragma unroll
+    for (int k = 0; k < FB_NX; ++k)
+#pragma unroll
+      for (int c = 3; c < 6; ++c) A[(pt * FB_NX + k) * FB_NX + c] = k == c ? 1.0 : 0.0;
+  }
+  // cost tiles, fb_linearize_kernel's expressions
+  const double* xp = x + ((size_t)b * (T + 1) + t) * FB_NX;
+  const double* up = u + pt * FB_NU;
+  if (kd < FB_NX) {
+    const int r = kd, q = r < FB_NQ ? r : 0;
+    lx[pt * FB_NX + r] = r < FB_NQ ? P.gx[q] * (P.tgt[q] - xp[q]) : 0.0;
+    for (int k = 0; k < FB_NX; ++k) lxx[(pt * FB_NX + r) * FB_NX + k] = (r == k && r < FB_NQ) ? P.hx[q] : 0.0;
+    if (t == T - 1) {  // (:142-143) at x_N
+      const double* xN = x + ((size_t)b * (T + 1) + T) * FB_NX;
+      lfx[(size_t)b * FB_NX + r] = r < FB_NQ ? P.gf[q] * (P.tgt[q] - xN[q]) : 0.0;
+      for (int k = 0; k < FB_NX; ++k)
+        lfxx[((size_t)b * FB_NX + r) * FB_NX + k] = (r == k && r < FB_NQ) ? P.hf[q] : 0.0;
+    }
+  }
+  if (kd >= ND - FB_NU) {
+    const int j = kd - (ND - FB_NU);
+    lu[pt * FB_NU + j] = P.gu[j] * up[j];
+    for (int k = 0; k < FB_NU; ++k) luu[(pt * FB_NU + j) * FB_NU + k] = j == k ? P.hu[j] : 0.0;
+  }
+}
+
 struct FbFwd {
   const double* x;
   const double* u;
@@ -1282,6 +1554,7 @@ struct ilqr_floating_handle {
   ilqr::FitState fit;  // the shared fit driver's state (ilqr_fit.h), costs in fp64
   double* slots = nullptr;  // the line search's trial slots (FbFwd::slots), cand per trajectory
   int cand = 4;             // line-search lanes per trajectory (fb_cand)
+  int32_t lin = ILQR_LINEARIZE_DUAL;  // ilqr_floating_set_linearization
 };
 
 namespace {
@@ -1394,7 +1667,29 @@ hipError_t fb_forward(ilqr_floating_handle* h, const ilqr::FbFwd& fa) {
   return hipGetLastError();
 }
 
+// the trial slots' doubles: B·cand rollouts, and never less than one point's record of the
+// analytic linearisation, whose scratch they are (fb_linearize)
+size_t fb_slot_doubles(int B, int T, int cand) {
+  const size_t n = (size_t)B * cand * ((size_t)(T + 1) * ilqr::FB_NX + (size_t)T * ilqr::FB_NU);
+  return n < (size_t)ilqr::FB_AN_NP ? (size_t)ilqr::FB_AN_NP : n;
+}
+
 hipError_t fb_linearize(ilqr_floating_handle* h, const double* x, const double* u, const int32_t* st) {
+  if (h->lin == ILQR_LINEARIZE_ANALYTIC) {
+    // the points in chunks of as many as the trial slots hold records of (the slots are the
+    // forward's, idle here: at least 96 doubles a point, a record is FB_AN_NP)
+    const size_t npt = (size_t)h->batch * h->T;
+    const size_t cap = fb_slot_doubles(h->batch, h->T, h->cand) / ilqr::FB_AN_NP;
+    for (size_t p0 = 0; p0 < npt; p0 += cap) {
+      const size_t n = npt - p0 < cap ? npt - p0 : cap;
+      ilqr::fb_analytic_primal_kernel<<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(h->model_dev, h->T, p0, n, x, u,
+                                                                                         st, h->slots);
+      const unsigned g = (unsigned)((n * ilqr::FB_LIN_DIRS + 255) / 256);
+      ilqr::fb_analytic_tangent_kernel<<<g, 256, 0, h->stream>>>(h->model_dev, h->T, p0, n, x, u, st, h->slots, h->A, h->Bm,
+                                                                 h->lx, h->lu, h->lxx, h->luu, h->lfx, h->lfxx);
+    }
+    return hipGetLastError();
+  }
   const size_t lanes = (size_t)h->batch * h->T * ilqr::FB_LIN_DIRS;
   ilqr::fb_linearize_kernel<<<(unsigned)((lanes + 255) / 256), 256, 0, h->stream>>>(
       h->model_dev, h->batch, h->T, x, u, st, h->A, h->Bm, h->lx, h->lu, h->lxx, h->luu, h->lfx, h->lfxx);
@@ -1456,7 +1751,7 @@ ilqr_status ilqr_floating_create(ilqr_floating_handle** out, int device, const i
   alloc(&h->move, 4 * B);
   if (e == hipSuccess) e = ilqr::fit_state_create(&h->fit, B, 8);
   h->cand = fb_cand(batch, T);
-  alloc(&h->slots, 8 * B * h->cand * ((T + 1) * nx + (size_t)T * nu));
+  alloc(&h->slots, 8 * fb_slot_doubles(batch, T, h->cand));
   alloc(&h->model_dev, sizeof(ilqr::FbModel));
   if (e == hipSuccess) e = hipMemcpy(h->model_dev, &h->model, sizeof(ilqr::FbModel), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
@@ -1485,6 +1780,20 @@ ilqr_status ilqr_floating_set_stream(ilqr_floating_handle* h, void* s) {
   h->stream = (hipStream_t)s;
   return ILQR_OK;
 }
+
+ilqr_status ilqr_floating_set_linearization(ilqr_floating_handle* h, int32_t linearization) {
+  if (!h) return ILQR_ERR_BAD_ARG;
+  if (linearization == ILQR_LINEARIZE_CENTRAL_FD) {
+    g_fb_error = "ilqr_floating_set_linearization: the floating-base family has no finite-difference "
+                 "linearisation (ILQR_LINEARIZE_DUAL or ILQR_LINEARIZE_ANALYTIC)";
+    return ILQR_ERR_UNSUPPORTED;
+  }
+  if (linearization != ILQR_LINEARIZE_DUAL && linearization != ILQR_LINEARIZE_ANALYTIC) return ILQR_ERR_BAD_ARG;
+  h->lin = linearization;
+  return ILQR_OK;
+}
+
+int32_t ilqr_floating_get_linearization(const ilqr_floating_handle* h) { return h ? h->lin : -1; }
 
 ilqr_status ilqr_floating_sync(ilqr_floating_handle* h) {
   if (!h) return ILQR_ERR_BAD_ARG;

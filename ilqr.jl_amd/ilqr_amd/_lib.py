@@ -55,7 +55,7 @@ F64 = 0
 F32 = 1
 LINEARIZE_DUAL = 0
 LINEARIZE_CENTRAL_FD = 1
-LINEARIZE_ANALYTIC = 2   # chains of 4 to 7 joints in F64 (the tiles path)
+LINEARIZE_ANALYTIC = 2   # chains of 4 to 7 joints in F64 (the tiles path); the floating family
 CHAIN_DYN_AUTO = 0          # ilqr_chain_dynamics_mode
 CHAIN_DYN_RNEA = 1
 CHAIN_DYN_CLOSED_FORM = 2
@@ -190,6 +190,8 @@ SIGNATURES = {
     "ilqr_floating_destroy": (C.c_int, [P]),
     "ilqr_floating_set_stream": (C.c_int, [P, P]),
     "ilqr_floating_sync": (C.c_int, [P]),
+    "ilqr_floating_set_linearization": (C.c_int, [P, C.c_int32]),
+    "ilqr_floating_get_linearization": (C.c_int32, [P]),
     "ilqr_floating_dynamics": (C.c_int, [P, P, P, P, C.c_int]),
     "ilqr_floating_linearize": (C.c_int, [P, P, P, P, P]),
     "ilqr_floating_backward": (C.c_int, [P, C.POINTER(Options), P, P, P, P, P]),

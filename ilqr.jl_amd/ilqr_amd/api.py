@@ -139,8 +139,9 @@ def _floating_solver(xb, ub, dynamicsf, immediate_cost, final_cost):
     if (p.nx, p.nu) != (nx, nu):
         raise AssertionError(f"problem is ({p.nx}, {p.nu}) but x/u are ({nx}, {nu})")
     dev = _device()
-    return _cache.workspace(("floating", dev, bytes(p.struct()), M, nb),
-                            lambda: FloatingSolver(p, M, nb, device=dev))
+    lin = dynamicsf.linearization   # part of the key: a dual and an analytic caller never share
+    return _cache.workspace(("floating", dev, bytes(p.struct()), M, nb, lin),
+                            lambda: FloatingSolver(p, M, nb, device=dev, linearization=lin))
 
 
 def clear_cache():

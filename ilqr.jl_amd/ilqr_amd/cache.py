@@ -2,6 +2,9 @@
 calls of the reference API — fit / backward_pass with arbitrary closures (the tiles
 handle) and linearize_dynamics on the device — so that an MPC loop calling them
 allocates no device workspace per call (include/ilqr.h: "hot calls never allocate").
+A key names everything a handle is created or configured with — family, device, model,
+shape and, for the floating-base family, the linearisation mode — so callers that differ
+in any of them never share a handle.
 
 A call checks its workspace OUT of the cache and back in when done, so two threads
 calling with the same shape at once never share one (the second builds its own; the

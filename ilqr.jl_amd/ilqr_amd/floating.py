@@ -20,6 +20,10 @@ oracle).
 
 `floating_closures(problem)` gives the reference-API callables: `ilqr_amd.fit` with them
 dispatches here.
+
+`linearization="analytic"` (FloatingSolver, FloatingDynamics, floating_closures) forms the
+same exact A, B from δν̇ = M⁻¹(δu − δ[ID(θ, ν, ν̇)]) instead of running the RK4 step in duals
+(ilqr_floating_set_linearization; faster, different rounding). The default is "dual".
 """
 from __future__ import annotations
 
@@ -107,10 +111,24 @@ def rbd_initial_state() -> np.ndarray:
     return np.array([0.0, 0.0, 1.0, 0.5, 0.75, 1.0, 0.0, 0.0] + [0.0] * 8)
 
 
-class FloatingSolver:
-    """Device-resident batched iLQR for one FloatingProblem (one ilqr_floating_handle)."""
+# linearization names (ilqr_linearization): "dual" (forward-mode duals, the default) or
+# "analytic" (the same Jacobians from the structure of ν̇ = M⁻¹(u − b)); the family has no "fd"
+_LIN = {"dual": _lib.LINEARIZE_DUAL, "analytic": _lib.LINEARIZE_ANALYTIC}
 
-    def __init__(self, problem: FloatingProblem, T: int, batch: int, device: int = 0):
+
+def _lin_code(name: str) -> int:
+    if name not in _LIN:
+        raise ValueError(f"linearization: 'dual' or 'analytic', not {name!r}")
+    return _LIN[name]
+
+
+class FloatingSolver:
+    """Device-resident batched iLQR for one FloatingProblem (one ilqr_floating_handle).
+    linearization: "dual" or "analytic" (set_linearization changes it between calls)."""
+
+    def __init__(self, problem: FloatingProblem, T: int, batch: int, device: int = 0,
+                 linearization: str = "dual"):
+        code = _lin_code(linearization)
         self.lib = _lib.load()
         self.p = problem
         self.nx, self.nu = problem.nx, problem.nu
@@ -121,6 +139,23 @@ class FloatingSolver:
         _lib.check(self.lib.ilqr_floating_create(C.byref(h), device, C.byref(self._s), T, batch),
                    "ilqr_floating_create")
         self.h = h
+        if code != _lib.LINEARIZE_DUAL:
+            try:
+                self.set_linearization(linearization)
+            except Exception:
+                self.close()
+                raise
+
+    @property
+    def linearization(self) -> str:
+        """The handle's mode: "dual" or "analytic"."""
+        code = self.lib.ilqr_floating_get_linearization(self.h)
+        return next(k for k, v in _LIN.items() if v == code)
+
+    def set_linearization(self, name: str):
+        """ilqr_floating_set_linearization: every later linearize / backward / fit uses it."""
+        _lib.check(self.lib.ilqr_floating_set_linearization(self.h, _lin_code(name)),
+                   "ilqr_floating_set_linearization")
 
     def close(self):
         if getattr(self, "h", None):
@@ -239,10 +274,13 @@ class FloatingDynamics:
     handle cached per (model, device) (cache.py: the reference script calls dynamicsf
     1000 times to build its state_traj, animate_RBD_2_link.jl:23-25). Device tensors
     stay on their device (and come back as tensors); anything else is evaluated on the
-    current device and comes back as a numpy array."""
+    current device and comes back as a numpy array. linearization: how ilqr_amd.fit /
+    backward_pass / helpers.linearize_dynamics form A and B with this callable."""
 
-    def __init__(self, problem: FloatingProblem):
+    def __init__(self, problem: FloatingProblem, linearization: str = "dual"):
+        _lin_code(linearization)
         self.problem = problem
+        self.linearization = linearization
 
     def __call__(self, x, u):
         from . import cache
@@ -250,9 +288,10 @@ class FloatingDynamics:
         dev = x.device if on_dev else torch.device("cuda", torch.cuda.current_device())
         xt = torch.as_tensor(x, dtype=torch.float64, device=dev).reshape(1, -1).contiguous()
         ut = torch.as_tensor(u, dtype=torch.float64, device=dev).reshape(1, -1).contiguous()
-        key = ("floating", dev.index, bytes(self.problem.struct()), 1, 1)
+        key = ("floating", dev.index, bytes(self.problem.struct()), 1, 1, self.linearization)
         with torch.cuda.device(dev), \
-                cache.workspace(key, lambda: FloatingSolver(self.problem, 1, 1, device=dev.index)) as s:
+                cache.workspace(key, lambda: FloatingSolver(self.problem, 1, 1, device=dev.index,
+                                                            linearization=self.linearization)) as s:
             y = s.dynamics(xt, ut)[0]
         return y if on_dev else y.cpu().numpy()
 
@@ -286,9 +325,10 @@ class FloatingFinalCost:
         return float(np.sum(e * np.asarray(p.qf_weight, float) * e) * p.qf_scale)
 
 
-def floating_closures(problem: FloatingProblem):
-    """(dynamicsf, immediate_cost, final_cost) of a FloatingProblem."""
-    return FloatingDynamics(problem), FloatingCost(problem), FloatingFinalCost(problem)
+def floating_closures(problem: FloatingProblem, linearization: str = "dual"):
+    """(dynamicsf, immediate_cost, final_cost) of a FloatingProblem; linearization ("dual" or
+    "analytic") rides on dynamicsf."""
+    return FloatingDynamics(problem, linearization), FloatingCost(problem), FloatingFinalCost(problem)
 
 
 def floating_problem_of(dynamicsf, immediate_cost, final_cost):

@@ -1049,10 +1049,23 @@ mutable struct FloatingSolver
     lock::ReentrantLock
 end
 
-function FloatingSolver(m::FloatingModel, T::Integer, batch::Integer; device::Integer=0)
+# `linearization = :dual` (forward-mode duals, the default) or `:analytic` (the same exact A, B
+# from δν̇ = M⁻¹(δu − δ[ID(θ, ν, ν̇)]): ilqr_floating_set_linearization), on FloatingSolver,
+# floating_closures and floating_fit; part of the FLOATING_CACHE key.
+function floating_linearization(l::Symbol)
+    l === :dual && return ILQR_LINEARIZE_DUAL
+    l === :analytic && return ILQR_LINEARIZE_ANALYTIC
+    throw(ArgumentError("linearization: :dual or :analytic, not :$l"))
+end
+
+function FloatingSolver(m::FloatingModel, T::Integer, batch::Integer; device::Integer=0, linearization::Symbol=:dual)
+    lin = floating_linearization(linearization)
     r = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:ilqr_floating_create, libilqr), Cint, (Ref{Ptr{Cvoid}}, Cint, Ref{FloatingModel}, Cint, Cint),
                 r, device, m, T, batch), "ilqr_floating_create")
+    st = ccall((:ilqr_floating_set_linearization, libilqr), Cint, (Ptr{Cvoid}, Int32), r[], lin)
+    st == ILQR_OK || (ccall((:ilqr_floating_destroy, libilqr), Cint, (Ptr{Cvoid},), r[]);
+                      check(st, "ilqr_floating_set_linearization"))
     nu = 6 + Int(m.n_joints); nx = 2 * nu; N = T + 1
     h = Handle(nx, nu, T, 1; device=device)  # device-memory helper only
     f(n) = alloc(h, Float64, batch * n)
@@ -1074,9 +1087,9 @@ function destroy!(s::FloatingSolver)
 end
 Base.close(s::FloatingSolver) = lock(() -> destroy!(s), s.lock)
 
-const FLOATING_CACHE = Dict{Tuple{FloatingModel,Int,Int},FloatingSolver}()
-floating_cached(f, m::FloatingModel, M::Integer, nb::Integer) =
-    with_cached(f, FLOATING_CACHE, () -> FloatingSolver(m, M, nb), (m, Int(M), Int(nb)))
+const FLOATING_CACHE = Dict{Tuple{FloatingModel,Int,Int,Symbol},FloatingSolver}()
+floating_cached(f, m::FloatingModel, M::Integer, nb::Integer, lin::Symbol=:dual) =
+    with_cached(f, FLOATING_CACHE, () -> FloatingSolver(m, M, nb; linearization=lin), (m, Int(M), Int(nb), lin))
 
 # -- the script's closures as callable structs (RBD_helper_functions.jl:48-116) -------------
 # fit / backward_pass / forward_pass / linearize_dynamics recognise the triple (family
@@ -1084,15 +1097,17 @@ floating_cached(f, m::FloatingModel, M::Integer, nb::Integer) =
 # the script's functions: dynamicsf one device RK4 step (a cached T = 1 workspace: the
 # script calls it 1000 times to build state_traj, animate_RBD_2_link.jl:23-25), the costs
 # plain Julia arithmetic (generic, as ForwardDiff needs them).
-struct FloatingDynamics; model::FloatingModel; end
+struct FloatingDynamics; model::FloatingModel; linearization::Symbol; end
+FloatingDynamics(m::FloatingModel) = FloatingDynamics(m, :dual)
 struct FloatingCost; model::FloatingModel; end
 struct FloatingFinalCost; model::FloatingModel; end
-floating_closures(m::FloatingModel=rbd_2dof_arm_floating()) = (FloatingDynamics(m), FloatingCost(m), FloatingFinalCost(m))
+floating_closures(m::FloatingModel=rbd_2dof_arm_floating(); linearization::Symbol=:dual) =
+    (floating_linearization(linearization); (FloatingDynamics(m, linearization), FloatingCost(m), FloatingFinalCost(m)))
 is_floating(f, l, lf) = f isa FloatingDynamics && l isa FloatingCost && lf isa FloatingFinalCost &&
                         f.model == l.model == lf.model
 
 function (f::FloatingDynamics)(x::AbstractVector, u::AbstractVector)            # dynamicsf (:48-79)
-    return floating_cached(f.model, 1, 1) do s
+    return floating_cached(f.model, 1, 1, f.linearization) do s
         upload!(s.h, s.x, Vector{Float64}(x)); upload!(s.h, s.u, Vector{Float64}(u))
         check(ccall((:ilqr_floating_dynamics, libilqr), Cint,
                     (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint), s.fh, s.x, s.u, s.xo, 1),
@@ -1119,7 +1134,7 @@ end
 # iLQR.fit (forward_pass.jl:148-179) of one trajectory (reference layout) on the device
 function floating_fit1(f::FloatingDynamics, x_init, u_init, x_traj, max_iter, tol, verbose)
     N, nx = size(x_init); M, nu = size(u_init)
-    return floating_cached(f.model, M, 1) do s
+    return floating_cached(f.model, M, 1, f.linearization) do s
         floating_shape(s, nx, nu)
         upload!(s.h, s.x, to_abi(x_init)); upload!(s.h, s.u, to_abi(u_init)); upload!(s.h, s.xt, to_abi(x_traj))
         o = default_options(); o.max_iter = max_iter; o.tol = tol
@@ -1143,7 +1158,7 @@ end
 # iLQR.backward_pass (backward_pass.jl:324-357) → (δu::T×nu, K::T×nu×nx)
 function floating_backward(f::FloatingDynamics, x, u)
     N, nx = size(x); M, nu = size(u)
-    return floating_cached(f.model, M, 1) do s
+    return floating_cached(f.model, M, 1, f.linearization) do s
         floating_shape(s, nx, nu)
         upload!(s.h, s.x, to_abi(x)); upload!(s.h, s.u, to_abi(u))
         check(ccall((:ilqr_floating_backward, libilqr), Cint,
@@ -1156,7 +1171,7 @@ end
 # iLQR.forward_pass (forward_pass.jl:55-93) → (x̄, ū, new_cost)
 function floating_forward(f::FloatingDynamics, x, u, x_traj, δu, K, prev_cost)
     N, nx = size(x); M, nu = size(u)
-    return floating_cached(f.model, M, 1) do s
+    return floating_cached(f.model, M, 1, f.linearization) do s
         floating_shape(s, nx, nu)
         upload!(s.h, s.x, to_abi(x)); upload!(s.h, s.u, to_abi(u)); upload!(s.h, s.xt, to_abi(x_traj))
         upload!(s.h, s.d, to_abi(δu)); upload!(s.h, s.K, gains_to_abi(K)); upload!(s.h, s.pc, Float64[prev_cost])
@@ -1175,7 +1190,7 @@ function floating_linearize(f::FloatingDynamics, x::AbstractMatrix, u::AbstractM
     M, nu = size(u); nx = size(x, 2)
     size(x, 1) in (M, M + 1) || throw(AssertionError("x has $(size(x, 1)) rows for $M inputs"))
     xa = size(x, 1) == M ? vcat(x, x[end:end, :]) : x                   # the ABI reads T+1 states
-    return floating_cached(f.model, M, 1) do s
+    return floating_cached(f.model, M, 1, f.linearization) do s
         floating_shape(s, nx, nu)
         if s.lA == C_NULL
             s.lA = alloc(s.h, Float64, s.M * s.nx * s.nx); s.lB = alloc(s.h, Float64, s.M * s.nx * s.nu)
@@ -1196,10 +1211,10 @@ x_init (16, T+1, batch) = [MRP; r; θ; ω; v; θ̇], u_init (8, T, batch), as th
 `state_traj` / `input_traj` transposed (animate_RBD_2_link.jl:19-25); on the cached
 FloatingSolver of (model, T, batch)."""
 function floating_fit(m::FloatingModel, x_init::Array{Float64,3}, u_init::Array{Float64,3};
-                      max_iter::Int64=100, tol::Float64=1e-6)
+                      max_iter::Int64=100, tol::Float64=1e-6, linearization::Symbol=:dual)
     nx, N, nb = size(x_init); nu = size(u_init, 1); M = N - 1
     @assert(size(u_init, 2) == M)
-    return floating_cached(m, M, nb) do s
+    return floating_cached(m, M, nb, linearization) do s
         floating_shape(s, nx, nu)
         upload!(s.h, s.x, x_init); upload!(s.h, s.u, u_init)
         o = default_options(); o.max_iter = max_iter; o.tol = tol

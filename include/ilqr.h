@@ -371,7 +371,8 @@ typedef enum { ILQR_F64 = 0, ILQR_F32 = 1 } ilqr_dtype;
 typedef enum {
   ILQR_LINEARIZE_DUAL = 0,
   ILQR_LINEARIZE_CENTRAL_FD = 1,
-  ILQR_LINEARIZE_ANALYTIC = 2 /* chains of 4 to 7 joints in ILQR_F64 only */
+  ILQR_LINEARIZE_ANALYTIC = 2 /* chains of 4 to 7 joints in ILQR_F64, and the floating-base
+                                 family (ilqr_floating_set_linearization) */
 } ilqr_linearization;
 
 typedef struct {
@@ -602,7 +603,11 @@ ilqr_status ilqr_host_free(void* ptr);
  * iLQR.fit (src/forward_pass.jl:148-179): linearize_dynamics in forward-mode duals
  * (ForwardDiff's algorithm), the cost tiles in closed form, the Riccati recursion of
  * ilqr_backward_tiles, forward_pass with its line search, and fit's bookkeeping, all on
- * the device.
+ * the device. ilqr_floating_set_linearization(h, ILQR_LINEARIZE_ANALYTIC) selects, for every
+ * call that linearises, the same exact Jacobians from δν̇ = M⁻¹(δu − δ[ID(θ, ν, ν̇)]) with ν̇
+ * held fixed (ν = [ω; v; θ̇], ID = M ν̇ + bias: one tangent Newton-Euler pass and one solve with
+ * the stage's factors per RK4 stage and direction, M never differentiated); they differ from
+ * the duals' by rounding only. A new handle is ILQR_LINEARIZE_DUAL.
  *   x = [p (MRP, 3); r (3); θ (n_joints); ω (3); v (3); θ̇ (n_joints)], the base twist
  *       (ω, v) in the base frame; u = [base torque (3); base force (3); joint torques]
  *   dynamicsf(x, u)     = RK4(dt) of [pdot_from_w(p, ω); v; θ̇; M(q) \ (u − bias(q, v))]
@@ -651,6 +656,14 @@ ilqr_status ilqr_floating_create(ilqr_floating_handle** out, int device, const i
 ilqr_status ilqr_floating_destroy(ilqr_floating_handle* h);
 ilqr_status ilqr_floating_set_stream(ilqr_floating_handle* h, void* hip_stream);
 ilqr_status ilqr_floating_sync(ilqr_floating_handle* h);
+/* How the handle forms A and B in ilqr_floating_linearize, _backward, _fit and _fit_ex:
+ * ILQR_LINEARIZE_DUAL (a new handle's) or ILQR_LINEARIZE_ANALYTIC. ILQR_LINEARIZE_CENTRAL_FD →
+ * ILQR_ERR_UNSUPPORTED (ilqr_floating_last_error says why), any other value and a NULL handle
+ * → ILQR_ERR_BAD_ARG; a refused value leaves the mode as it was. Allocates nothing, touches
+ * no device state and may be called between calls on the handle. The getter returns the
+ * mode, −1 for a NULL handle. */
+ilqr_status ilqr_floating_set_linearization(ilqr_floating_handle* h, int32_t linearization);
+int32_t ilqr_floating_get_linearization(const ilqr_floating_handle* h);
 /* dynamicsf for n independent (x, u) pairs: x (n, nx), u (n, nu) → x_next (n, nx) */
 ilqr_status ilqr_floating_dynamics(ilqr_floating_handle* h, const double* x, const double* u,
                                    double* x_next, int n);
