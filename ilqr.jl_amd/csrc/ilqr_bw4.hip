@@ -84,8 +84,10 @@ __device__ __forceinline__ double mf4n(double a, double b, double c) {
   return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 1);
 }
 
+// AUX: the load's cache-policy word (0 plain, 2 the " nt" hint)
+template <int AUX = 0>
 __device__ __forceinline__ double buf_ld(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
-  return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
+  return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, AUX));
 }
 __device__ __forceinline__ void buf_st(double v, __amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
   __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2v, v), r, voff, soff, 0);
@@ -149,23 +151,26 @@ __device__ __forceinline__ void bw4_ops_each(BW4Ops& o, FN&& fn) {
     for (int I = 0; I < 3; ++I) fn(o.S[K][I], i++);
 }
 
-template <int MODE>
-__device__ __forceinline__ unsigned lq_backward4_body(const BW4Ops& op, int b0, int B, unsigned active, int T,
-                                                      const double* __restrict__ x,
+template <int MODE, int KAUX>
+__device__ __forceinline__ unsigned lq_backward4_body(const BW4Ops& op, int b0, int B,
+                                                      unsigned active, int T, const double* __restrict__ x,
                                                       const double* __restrict__ u,
                                                       double* __restrict__ d_out, double* __restrict__ K_out,
-                                                      double* __restrict__ fac, double mu, double* lds);
+                                                      double* __restrict__ fac, double mu,
+                                                      double* lds ILQR_EDGE_PARAM);
 
 // `snap`: the handle's operand snapshots (BW4_STORE writes the wave's, BW4_CHECK compares
 // and, where it differs, rewrites it; nullptr: none kept). `rec`: per wave, 1 if the wave
 // reused the stored gains in this launch, 0 if it ran the full recursion (one store per
-// wave; nullptr: not recorded).
-template <int MODE>
+// wave; nullptr: not recorded). KAUX: the cache-policy word of the vector-only mode's K and
+// factor loads (buf_ld).
+template <int MODE, int KAUX = 0>
 __device__ unsigned lq_backward4_wave(const LQParams& P, int b0, int B, unsigned active, int T,
                                       const double* __restrict__ x, const double* __restrict__ u,
                                       double* __restrict__ d_out, double* __restrict__ K_out,
                                       double* __restrict__ fac, double mu, double* lds,
-                                      double* __restrict__ snap = nullptr, int32_t* __restrict__ rec = nullptr) {
+                                      double* __restrict__ snap = nullptr,
+                                      int32_t* __restrict__ rec = nullptr ILQR_EDGE_PARAM_DEF) {
   constexpr int NX = 12, NU = 4;
   b0 = __builtin_amdgcn_readfirstlane(b0);
   const int l = threadIdx.x & 63;
@@ -209,20 +214,22 @@ __device__ unsigned lq_backward4_wave(const LQParams& P, int b0, int B, unsigned
       same = sw && __ballot(diff != 0) == 0;  // wave-uniform
     }
     if (rec && l == 0) rec[b0 / BW4_SLOTS] = same ? 1 : 0;
-    if (same) return lq_backward4_body<BW4_VEC>(op, b0, B, active, T, x, u, d_out, K_out, fac, mu, lds);
+    if (same)
+      return lq_backward4_body<BW4_VEC, KAUX>(op, b0, B, active, T, x, u, d_out, K_out, fac, mu, lds ILQR_EDGE_PASS);
     if (sw) bw4_ops_each(op, [&](double& v, int i) { sw[i * 64] = __builtin_bit_cast(unsigned long long, v); });
-    return lq_backward4_body<BW4_STORE>(op, b0, B, active, T, x, u, d_out, K_out, fac, mu, lds);
+    return lq_backward4_body<BW4_STORE, 0>(op, b0, B, active, T, x, u, d_out, K_out, fac, mu, lds ILQR_EDGE_PASS);
   } else {
-    return lq_backward4_body<MODE>(op, b0, B, active, T, x, u, d_out, K_out, fac, mu, lds);
+    return lq_backward4_body<MODE, KAUX>(op, b0, B, active, T, x, u, d_out, K_out, fac, mu, lds ILQR_EDGE_PASS);
   }
 }
 
-template <int MODE>
-__device__ __forceinline__ unsigned lq_backward4_body(const BW4Ops& op, int b0, int B, unsigned active, int T,
-                                                      const double* __restrict__ x,
+template <int MODE, int KAUX>
+__device__ __forceinline__ unsigned lq_backward4_body(const BW4Ops& op, int b0, int B,
+                                                      unsigned active, int T, const double* __restrict__ x,
                                                       const double* __restrict__ u,
                                                       double* __restrict__ d_out, double* __restrict__ K_out,
-                                                      double* __restrict__ fac, double mu, double* lds) {
+                                                      double* __restrict__ fac, double mu,
+                                                      double* lds ILQR_EDGE_PARAM) {
   constexpr bool VEC = MODE == BW4_VEC, STORE = MODE == BW4_STORE;
   constexpr int NX = 12, NU = 4;
   const int l = threadIdx.x & 63;
@@ -298,9 +305,9 @@ __device__ __forceinline__ unsigned lq_backward4_body(const BW4Ops& op, int b0, 
   auto prefetch = [&](double (&q)[5], int tp) {
     tp = tp > 0 ? tp : 0;  // past step 0: step 0's again (never used)
 #pragma unroll
-    for (int J = 0; J < 3; ++J) q[J] = buf_ld(rK, kv + 32 * J, (uint32_t)(tp * NU * NX * 8));
-    q[3] = buf_ld(rF, fv, (uint32_t)(tp * BW4_FAC * 8));
-    q[4] = buf_ld(rF, fd, (uint32_t)(tp * BW4_FAC * 8));
+    for (int J = 0; J < 3; ++J) q[J] = buf_ld<KAUX>(rK, kv + 32 * J, (uint32_t)(tp * NU * NX * 8));
+    q[3] = buf_ld<KAUX>(rF, fv, (uint32_t)(tp * BW4_FAC * 8));
+    q[4] = buf_ld<KAUX>(rF, fd, (uint32_t)(tp * BW4_FAC * 8));
   };
   if constexpr (VEC) {
 #pragma unroll
@@ -348,6 +355,7 @@ __device__ __forceinline__ unsigned lq_backward4_body(const BW4Ops& op, int b0, 
   // every load of the prologue lands here, so the loop's waits only count the loop's
   // own loads
   __builtin_amdgcn_s_waitcnt(0);
+  ILQR_EDGE(EDGE_BW_PRO);
   lz_block(T - 1);
 
   // lane-permutation sources of the L z columns, one per step of a block of four
@@ -552,6 +560,7 @@ __device__ __forceinline__ unsigned lq_backward4_body(const BW4Ops& op, int b0, 
   if (t >= 0) step(t, I0{});
   if (t >= 1) step(t - 1, I1{});
   if (t >= 2) step(t - 2, I2{});
+  ILQR_EDGE(EDGE_BW_END);
   bool nan = false;
 #pragma unroll
   for (int J = 0; J < 4; ++J) nan |= __builtin_isnan(Klast[J]);
@@ -620,6 +629,19 @@ template <bool MF, int BW>
 __device__ __forceinline__ void lq_iter_fused4(const LQParams& P, int B, int T, const IterArgs& a,
                                                const LSParams& ls, double* lds_all) {
   static_assert(FUSED_LDS >= BW4_LDS, "backward scratch fits the ring");
+  // Cache policy of K on the gain-reuse path (BW4_VEC, and BW4_CHECK whose common branch
+  // it is), where every K line is read six times a fit, ≈45 µs apart, and not once as in
+  // the other modes: the forward's first slot load goes without its " nt" hint, the
+  // backward's K / factor loads stay plain (measured: ilqr_fwd_ring.h's cache-policy note,
+  // DESIGN.md §4, profiles/reuse_edges/README.md).
+  constexpr bool REUSE = BW == BW4_VEC || BW == BW4_CHECK;
+  constexpr bool FW_K1_NT = !REUSE;
+  constexpr int BW_KAUX = 0;
+#ifdef ILQR_COOP_TRACE
+  EdgeStamps est{};
+  EdgeStamps* const es = &est;
+#endif
+  ILQR_EDGE(EDGE_ENTRY);
   const int w = threadIdx.x >> 6;
   double* lds = lds_all + w * FUSED_LDS;
   const int wid = blockIdx.x * FUSED_WAVES + w;
@@ -661,7 +683,9 @@ __device__ __forceinline__ void lq_iter_fused4(const LQParams& P, int B, int T, 
   }
   if (active != 0) {
     const unsigned nan =
-        lq_backward4_wave<BW>(P, b0, B, active, T, a.x, a.u, a.d, a.K, a.fac, ls.mu, lds, a.snap, a.branch) & active;
+        lq_backward4_wave<BW, BW_KAUX>(P, b0, B, active, T, a.x, a.u, a.d, a.K, a.fac, ls.mu, lds, a.snap,
+                                       a.branch ILQR_EDGE_PASS) &
+        active;
     if (owner && ((nan >> q) & 1u)) {
       a.status[b0 + q] = ILQR_TRAJ_NAN;  // reference: AssertionError at backward_pass.jl:353
       if (a.res_parity) a.res_parity[b0 + q] = a.parity;
@@ -670,15 +694,27 @@ __device__ __forceinline__ void lq_iter_fused4(const LQParams& P, int B, int T, 
     // and the LDS scratch free for the ring
     __builtin_amdgcn_s_waitcnt(0);
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    ILQR_EDGE(EDGE_TURN);
     const unsigned run = active & ~nan;
     if constexpr (MF)
       iter_forward_wave_mfma(P, b0, B, T, ai, ls, lds, run);
     else if (coop)
-      own = iter_forward_wave_coop<12, 4>(P, b0, B, T, ai, ls, lds, ((run >> (l >> 4)) & 1u) != 0);
+      own = iter_forward_wave_coop<12, 4, FW_K1_NT>(P, b0, B, T, ai, ls, lds,
+                                                    ((run >> (l >> 4)) & 1u) != 0 ILQR_EDGE_PASS);
     else
-      iter_forward_wave_active<12, 4>(P, b0, B, T, ai, ls, lds, ((run >> (l >> 4)) & 1u) != 0);
+      iter_forward_wave_active<12, 4, true, FW_K1_NT>(P, b0, B, T, ai, ls, lds,
+                                                      ((run >> (l >> 4)) & 1u) != 0 ILQR_EDGE_PASS);
   }
   if (coop) lq_coop_search<12, 4>(P, B, T, ai, ls, lds, wid, b0, own);
+#ifdef ILQR_COOP_TRACE
+  // the wave's stamps: three records (kinds 4, 5, 6; generation = the fit's iteration)
+  ILQR_EDGE(EDGE_EXIT);
+  if (l == 0) {
+    coop_trace(4, a.iter, wid, 0, 0, 0, est.t[EDGE_ENTRY], est.t[EDGE_BW_PRO], est.t[EDGE_BW_END]);
+    coop_trace(5, a.iter, wid, 0, 0, 0, est.t[EDGE_TURN], est.t[EDGE_FW_SLOT0], est.t[EDGE_FW_END]);
+    coop_trace(6, a.iter, wid, 0, 0, 0, est.t[EDGE_FW_QF], est.t[EDGE_EXIT], 0);
+  }
+#endif
 }
 
 #define ILQR_FUSED4_KERNEL(NAME, BW)                                                                  \

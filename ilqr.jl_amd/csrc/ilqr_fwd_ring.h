@@ -134,8 +134,65 @@ __device__ __forceinline__ double dpp_dot16_bd(double src, const double (&c)[12]
 // slot layout with both K loads pure and hinted measured 52.6 µs. Row broadcasts
 // through LDS instead of DPP gave the same bits and measured slower. (These alternates
 // and the forward's timing-only ablations live in tools/ablation/restore_alternates.patch.)
+// "Read once" holds where K is computed and consumed in one launch (the stand-alone
+// forward, the fused kernel's full and storing modes, the candidate passes). On the
+// gain-reuse path the same K lines are read six times a fit, ≈45 µs apart, and there the
+// hint costs: the fused vector-only kernel's forward runs its first load plain
+// (lq_forward_wave_ring's K1_NT = false; the backward that follows re-reads those lines
+// and its loop went from 37.6 to 34.4 µs), worth +120 to +300 it/s on a headline of
+// 10,100 as the only difference; " nt" on the vector-only backward's K and factor loads
+// instead lost 12-14 % (profiles/reuse_edges/README.md,
+// tools/ablation/reuse_edges_alternates.patch).
 #define ILQR_FW_LDS_OP1 "global_load_lds_dwordx4 %0, off nt"
 #define ILQR_FW_LDS_OP "global_load_lds_dwordx4 %0, off"
+
+// Trace build (ILQR_COOP_TRACE, the Makefile's `tracevariant`; never the product, which
+// compiles none of this): lane 0 of every wave of the fused iteration stamps the 100 MHz
+// real-time counter at the edges of its two step loops. The stamps stay in registers (a
+// store inside the forward would join the ring's vmcnt bookkeeping) and leave at the
+// kernel's exit as three coop_trace records; tools/phase_edges.py reads them back.
+#ifdef ILQR_COOP_TRACE
+enum {
+  EDGE_ENTRY,     // kernel entry
+  EDGE_BW_PRO,    // the backward prologue's loads have landed
+  EDGE_BW_END,    // after the backward's last step
+  EDGE_TURN,      // after the turn's wait and fence
+  EDGE_FW_SLOT0,  // slot 0 of the first trial has landed (its read_slot(0) is next)
+  EDGE_FW_END,    // after the first trial's last step
+  EDGE_FW_QF,     // the first trial's Qf row is in registers
+  EDGE_EXIT,
+  EDGE_N
+};
+struct EdgeStamps {
+  unsigned long long t[EDGE_N];
+};
+#define ILQR_EDGE_PARAM , EdgeStamps* es
+#define ILQR_EDGE_PARAM_DEF , EdgeStamps* es = nullptr
+#define ILQR_EDGE_PASS , es
+// one statement, its own wait inside (s_memrealtime returns through lgkmcnt)
+#define ILQR_EDGE(i)                                                                                 \
+  do {                                                                                               \
+    if (es) asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(es->t[i])::"memory");     \
+  } while (0)
+// the same once every load in flight has landed
+#define ILQR_EDGE_VM0(i)                                       \
+  do {                                                         \
+    if (es) {                                                  \
+      __builtin_amdgcn_s_waitcnt((0) | (7 << 4) | (15 << 8));  \
+      ILQR_EDGE(i);                                            \
+    }                                                          \
+  } while (0)
+#else
+#define ILQR_EDGE_PARAM
+#define ILQR_EDGE_PARAM_DEF
+#define ILQR_EDGE_PASS
+#define ILQR_EDGE(i) \
+  do {               \
+  } while (0)
+#define ILQR_EDGE_VM0(i) \
+  do {                   \
+  } while (0)
+#endif
 
 struct FwdOut {
   double cost;
@@ -189,14 +246,17 @@ constexpr int RING_LAREA = 4 * 160 + 16 + 4 * 64;
 //
 // CAND: one candidate pass (CandPass above) of trajectory b0 in all four groups — no
 // search loop; the result is this group's cost, du2 and eo.
-template <int NX, int NU, int R, int PF, bool LR_REGS = true, bool CAND = false>
+//
+// K1_NT: the slot's first load (64 of the step's 96 K chunks) carries the " nt" hint
+// (the cache-policy note above).
+template <int NX, int NU, int R, int PF, bool LR_REGS = true, bool CAND = false, bool K1_NT = true>
 __device__ FwdOut lq_forward_wave_ring(const LQParams& P, int b0, int B, int T, bool active,
                                        const double* __restrict__ x, const double* __restrict__ u,
                                        const double* __restrict__ xtraj, const double* __restrict__ dg,
                                        const double* __restrict__ Kg, double prev_cost,
                                        double* __restrict__ xnew, double* __restrict__ unew,
                                        double* du2_out, const LSParams& ls, double* ring,
-                                       const CandPass& cand = CandPass{0.0, -1}) {
+                                       const CandPass& cand = CandPass{0.0, -1} ILQR_EDGE_PARAM_DEF) {
   static_assert(NX == 12 && NU == 4, "slot layout and lane map are written for nx = 12, nu = 4");
   static_assert(R > PF && PF >= 1, "the slot being refilled must not be the one being read");
   constexpr uint32_t OOR = 0x80000000u;
@@ -227,10 +287,23 @@ __device__ FwdOut lq_forward_wave_ring(const LQParams& P, int b0, int B, int T, 
   // the cost Hessian rows live in LDS after the ring (re-read every step: registers
   // are the scarce resource): trajectory g's Q at 160g, R at 160g + 144
   double* const Ls = ring + R * RING_SLOT;
-  for (int i = l; i < 4 * 160; i += 64) {
-    const int gg = i / 160, e = i % 160;
-    const size_t bt = (size_t)b0 + (gg < nt ? gg : 0);
-    Ls[i] = e < NX * NX ? P.Q[bt * NX * NX + e] : P.R[bt * NU * NU + (e < NX * NX ? 0 : e - NX * NX)];
+  {
+    // every load issued before the first is waited for: as a rolled loop with the Q / R
+    // choice as a branch this was ten round trips in series with nothing else in flight,
+    // 5.2 µs of forward prologue at B = 4096 against 2.3 (profiles/reuse_edges/)
+    static_assert(4 * 160 % 64 == 0, "whole passes of the wave");
+    double lv[4 * 160 / 64];
+#pragma unroll
+    for (int k = 0; k < 4 * 160 / 64; ++k) {
+      const int i = l + 64 * k, gg = i / 160, e = i % 160;
+      const size_t bt = (size_t)b0 + (gg < nt ? gg : 0);
+      const double* p = e < NX * NX ? P.Q + bt * NX * NX + e : P.R + bt * NU * NU + (e - NX * NX);
+      asm volatile("" : "+v"(p));  // one address, one load: no branch per source
+      typedef __attribute__((address_space(1))) const double gdouble;  // a global load, not flat
+      lv[k] = *(gdouble*)p;
+    }
+#pragma unroll
+    for (int k = 0; k < 4 * 160 / 64; ++k) Ls[l + 64 * k] = lv[k];
   }
   const int la = is_x ? g * 160 + jx * NX : g * 160 + NX * NX + iu * NU;  // this lane's L row
   double Lk[NX];  // the cost row in registers (LR_REGS)
@@ -308,7 +381,10 @@ __device__ FwdOut lq_forward_wave_ring(const LQParams& P, int b0, int B, int T, 
     uint32_t tt = (uint32_t)(t < T ? t : T - 1);  // clamped: loaded, never read
     asm volatile("" : "+s"(tt));  // no hoisting of the prologue's addresses out of the trial loop
     const uint32_t m0 = ring_lds + (uint32_t)((t % R) * RING_SLOT * 8);
-    asm volatile(ILQR_FW_LDS_OP1 ::"v"(p1 + (size_t)tt * s1), "{m0}"(m0) : "memory");
+    if constexpr (K1_NT)
+      asm volatile(ILQR_FW_LDS_OP1 ::"v"(p1 + (size_t)tt * s1), "{m0}"(m0) : "memory");
+    else
+      asm volatile(ILQR_FW_LDS_OP ::"v"(p1 + (size_t)tt * s1), "{m0}"(m0) : "memory");
     if constexpr (!CAND) {
       asm volatile(ILQR_FW_LDS_OP ::"v"(p2 + (size_t)tt * s2), "{m0}"(m0 + 1024) : "memory");
       asm volatile(ILQR_FW_LDS_OP ::"v"(p3 + (size_t)tt * s3), "{m0}"(m0 + 2048) : "memory");
@@ -379,6 +455,7 @@ __device__ FwdOut lq_forward_wave_ring(const LQParams& P, int b0, int B, int T, 
     };
     Slot cur;
     wait_slot(std::integral_constant<int, N_PRO>{});
+    if (trial == 1) ILQR_EDGE(EDGE_FW_SLOT0);
     read_slot(0, cur);
     double xb = is_x ? cur.a : 0.0;  // x̄₁ = x₁ (:65)
     auto step = [&](int t, auto next_wait) {
@@ -423,7 +500,10 @@ __device__ FwdOut lq_forward_wave_ring(const LQParams& P, int b0, int B, int T, 
     for (int t = 0; t < tp - 1; ++t) step(t, std::integral_constant<int, N_PRO>{});
     for (int t = tp - 1; t < T; ++t) step(t, std::integral_constant<int, N_SS>{});
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2v, xb), rXN, ox, (uint32_t)T * NX * 8, 0);
+    if (trial == 1) ILQR_EDGE(EDGE_FW_END);
     // Qf row (x lanes; u lanes read row 0 and zero it): one base address, 6 × 16 B
+    // (loaded in the prologue and kept over the trials instead, the round trip goes from
+    // here but the headline does not gain: profiles/reuse_edges/README.md)
     const double2* qrow = reinterpret_cast<const double2*>(Qfb + jx * NX);
     asm volatile("" : "+v"(qrow));  // keep the row address from being hoisted as 12 pointers
     double Qfr[NX];
@@ -433,6 +513,7 @@ __device__ FwdOut lq_forward_wave_ring(const LQParams& P, int b0, int B, int T, 
       Qfr[2 * k] = is_x ? q.x : 0.0;
       Qfr[2 * k + 1] = is_x ? q.y : 0.0;
     }
+    if (trial == 1) ILQR_EDGE_VM0(EDGE_FW_QF);
     const double lf = dpp_dot12(is_x ? xb : 0.0, Qfr);
     cost = fma(is_x ? xb : 0.0, lf, cost);
     cost = rowsum16(cost);
@@ -1005,17 +1086,18 @@ constexpr int PIPE_R = 8, PIPE_PF = 7;
 // forward pass + convergence test (:163-175) of the wave's trajectories b0 .. b0+3;
 // called by the whole wave, groups whose status is not OK (or past B) sit out
 // (`active`: this lane's group runs; the caller read it from status)
-template <int NX, int NU, bool LR_REGS = true>
+// (K1_NT: lq_forward_wave_ring's)
+template <int NX, int NU, bool LR_REGS = true, bool K1_NT = true>
 __device__ __forceinline__ void iter_forward_wave_active(const LQParams& P, int b0, int B, int T,
                                                          const IterArgs& a, const LSParams& ls,
-                                                         double* ring, bool active) {
+                                                         double* ring, bool active ILQR_EDGE_PARAM_DEF) {
   const int j = threadIdx.x & 15;
   const int b = b0 + ((threadIdx.x & 63) >> 4);
   double du2 = 0.0;
   const double pc = (a.prev_cost && active) ? a.prev_cost[b] : INFINITY;
-  const FwdOut r = lq_forward_wave_ring<NX, NU, PIPE_R, PIPE_PF, LR_REGS>(P, b0, B, T, active, a.x, a.u,
-                                                                 a.xtraj, a.d, a.K, pc, a.xnew,
-                                                                 a.unew, &du2, ls, ring);
+  const FwdOut r = lq_forward_wave_ring<NX, NU, PIPE_R, PIPE_PF, LR_REGS, false, K1_NT>(
+      P, b0, B, T, active, a.x, a.u, a.xtraj, a.d, a.K, pc, a.xnew, a.unew, &du2, ls, ring,
+      CandPass{0.0, -1} ILQR_EDGE_PASS);
   if (j == 0 && active) {
     if (a.trials) a.trials[b] = r.trials;
     if (a.du2) a.du2[b] = du2;
@@ -1525,18 +1607,21 @@ __device__ void lq_coop_search(const LQParams& P, int B, int T, const IterArgs& 
 // The fused iteration's forward with the cooperative search: trial 1 in the wave's own
 // groups (the ring forward's sequential code at max_trials = 1); an accepted trajectory
 // is done as in iter_forward_wave_active, an open one is published.
-template <int NX, int NU>
+// (K1_NT: lq_forward_wave_ring's, for the wave's own trial 1; the candidate passes keep
+// the hint)
+template <int NX, int NU, bool K1_NT = true>
 __device__ __forceinline__ unsigned iter_forward_wave_coop(const LQParams& P, int b0, int B, int T,
                                                            const IterArgs& a, const LSParams& ls,
-                                                           double* ring, bool active) {
+                                                           double* ring, bool active ILQR_EDGE_PARAM_DEF) {
   const int j = threadIdx.x & 15;
   const int b = b0 + ((threadIdx.x & 63) >> 4);
   LSParams ls1 = ls;
   ls1.max_trials = 1;
   double du2 = 0.0;
   const double pc = (a.prev_cost && active) ? a.prev_cost[b] : INFINITY;
-  const FwdOut r = lq_forward_wave_ring<NX, NU, PIPE_R, PIPE_PF>(P, b0, B, T, active, a.x, a.u, a.xtraj, a.d,
-                                                                 a.K, pc, a.xnew, a.unew, &du2, ls1, ring);
+  const FwdOut r = lq_forward_wave_ring<NX, NU, PIPE_R, PIPE_PF, true, false, K1_NT>(
+      P, b0, B, T, active, a.x, a.u, a.xtraj, a.d, a.K, pc, a.xnew, a.unew, &du2, ls1, ring,
+      CandPass{0.0, -1} ILQR_EDGE_PASS);
   if (j == 0 && active) {
     if (!r.accepted) {
       coop_publish(*a.coop, a.coop_gen, b, ls.max_trials);  // status stays OK until finalised
