@@ -84,6 +84,11 @@ struct ilqr_handle {
   bool reuse_valid = false;
   double reuse_mu = 0.0;
   bool check_now = false;  // ilqr_fit_ex → enqueue_iteration: this fit's first launch checks
+  // ILQR_TRACK_CONSISTENT (ilqr_set_tracking): the backward of ilqr_iterate / ilqr_fit takes
+  // lx_t from x_t − x_traj_t (IterArgs::track). x_traj is vector-side data: the stored gains,
+  // the factor and the snapshot do not depend on it, so neither the mode nor a new reference
+  // touches reuse_valid
+  bool track = false;
   ilqr::LSCoopRec* coop_rec = nullptr;
   double* coop_cost = nullptr;
   double* coop_du2 = nullptr;
@@ -175,6 +180,11 @@ ilqr_status check_problem(const ilqr_handle* h, const ilqr_problem* p) {
 }
 
 bool two_link(const ilqr_problem* p) { return p->kind == ILQR_PROBLEM_TWO_LINK; }
+
+// the consistent tracking mode is the LQ family's (the 2-link family: a follow-up)
+ilqr_status check_tracking(const ilqr_handle* h, const ilqr_problem* p) {
+  return h->track && two_link(p) ? ILQR_ERR_UNSUPPORTED : ILQR_OK;
+}
 
 bool padded(const ilqr_handle* h, const ilqr_problem* p) {
   return p->kind == ILQR_PROBLEM_LQ && lq_paddable(h->nx, h->nu);
@@ -285,6 +295,7 @@ ilqr_status ensure_pad(ilqr_handle* h) {
   h->pad->coop = h->coop;
   h->pad->full_bw = h->full_bw;
   h->pad->per_call = h->per_call;
+  h->pad->track = h->track;
   return ILQR_OK;
 }
 
@@ -576,6 +587,17 @@ ilqr_status ilqr_set_schedule(ilqr_handle* h, int flags) {
   return ILQR_OK;
 }
 
+ilqr_status ilqr_set_tracking(ilqr_handle* h, int32_t mode) {
+  if (!h || (mode != ILQR_TRACK_FORWARD_ONLY && mode != ILQR_TRACK_CONSISTENT)) return ILQR_ERR_BAD_ARG;
+  for (ilqr_handle* t : {h, h->pad})
+    if (t) t->track = mode == ILQR_TRACK_CONSISTENT;
+  return ILQR_OK;
+}
+
+int32_t ilqr_get_tracking(const ilqr_handle* h) {
+  return !h ? -1 : (h->track ? ILQR_TRACK_CONSISTENT : ILQR_TRACK_FORWARD_ONLY);
+}
+
 ilqr_status ilqr_sync(ilqr_handle* h) {
   if (!h) return ILQR_ERR_BAD_ARG;
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -585,10 +607,18 @@ ilqr_status ilqr_sync(ilqr_handle* h) {
 ilqr_status ilqr_backward(ilqr_handle* h, const ilqr_problem* p, const ilqr_options* o,
                           const double* x, const double* u, double* d, double* K,
                           int32_t* status) {
+  return ilqr_backward_tracking(h, p, o, x, u, nullptr, d, K, status);
+}
+
+// x_traj == nullptr: ilqr_backward itself (every family, the plain kernels)
+ilqr_status ilqr_backward_tracking(ilqr_handle* h, const ilqr_problem* p, const ilqr_options* o,
+                                   const double* x, const double* u, const double* x_traj,
+                                   double* d, double* K, int32_t* status) {
   ilqr_status st = check_problem(h, p);
   if (st != ILQR_OK) return st;
   if ((st = ilqr::check_options(o)) != ILQR_OK) return st;
   if (!x || !u || !d || !K) return ILQR_ERR_BAD_ARG;
+  if (x_traj && two_link(p)) return ILQR_ERR_UNSUPPORTED;
   HIP_TRY(hipSetDevice(h->device));
   if (padded(h, p)) {
     ILQR_TRY(ensure_pad(h));
@@ -596,8 +626,10 @@ ilqr_status ilqr_backward(ilqr_handle* h, const ilqr_problem* p, const ilqr_opti
     ILQR_TRY(pad_problem(h, p, &pp));
     ILQR_TRY(pad_x(h, x, h->px));
     ILQR_TRY(pad_u(h, u, h->pu));
+    if (x_traj) ILQR_TRY(pad_x(h, x_traj, h->pxt));
     // with a status array the inner call folds it (and synchronises)
-    const ilqr_status bst = ilqr_backward(h->pad, &pp, o, h->px, h->pu, h->pd, h->pK, status);
+    const ilqr_status bst = ilqr_backward_tracking(h->pad, &pp, o, h->px, h->pu, x_traj ? h->pxt : nullptr,
+                                                   h->pd, h->pK, status);
     if (bst != ILQR_OK && bst != ILQR_ERR_NAN) return bst;
     ILQR_TRY(unpad_u(h, h->pd, d));
     ILQR_TRY(unpad3(h, h->pK, K, (size_t)h->batch * h->T, h->nu, h->nx, PAD_NU, PAD_NX));
@@ -609,7 +641,7 @@ ilqr_status ilqr_backward(ilqr_handle* h, const ilqr_problem* p, const ilqr_opti
                                      status, ilqr::ls_params(o).mu, h->stream));
   else
     HIP_TRY(ilqr::launch_lq_backward(h->nx, h->nu, lq_params(p), h->batch, h->T, x, u, d, K,
-                                     status, ilqr::ls_params(o).mu, h->stream, h->bw_wave));
+                                     status, ilqr::ls_params(o).mu, h->stream, h->bw_wave, x_traj));
   if (status) HIP_TRY(ilqr::fold_status(status, h->batch, h->stream, h->host_status, &st));
   return st;
 }
@@ -695,6 +727,7 @@ ilqr_status ilqr_iterate(ilqr_handle* h, const ilqr_problem* p, const ilqr_optio
   if (st != ILQR_OK) return st;
   if ((st = ilqr::check_options(o)) != ILQR_OK) return st;
   if (!x || !u || !x_new || !u_new || !new_cost || !status) return ILQR_ERR_BAD_ARG;
+  if ((st = check_tracking(h, p)) != ILQR_OK) return st;
   HIP_TRY(hipSetDevice(h->device));
   if (padded(h, p)) {
     ILQR_TRY(ensure_pad(h));
@@ -726,6 +759,7 @@ ilqr_status ilqr_iterate(ilqr_handle* h, const ilqr_problem* p, const ilqr_optio
   a.iters = nullptr;
   a.parity = 0;
   a.iter = 0;
+  a.track = h->track;
   return enqueue_iteration(h, p, a, ilqr::ls_params(o), /*chain=*/false);
 }
 
@@ -745,6 +779,7 @@ ilqr_status ilqr_fit_ex(ilqr_handle* h, const ilqr_problem* p, const ilqr_option
   if (st != ILQR_OK) return st;
   if ((st = ilqr::check_options(o)) != ILQR_OK) return st;
   if (!x_init || !u_init || !x_out || !u_out) return ILQR_ERR_BAD_ARG;
+  if ((st = check_tracking(h, p)) != ILQR_OK) return st;
   ilqr_options def;
   ilqr_default_options(&def);
   if (!o) o = &def;
@@ -814,6 +849,7 @@ ilqr_status ilqr_fit_ex(ilqr_handle* h, const ilqr_problem* p, const ilqr_option
     a.parity = b.parity;
     a.iter = it;
     a.init = init_in_iter && it == 1;
+    a.track = h->track;
     // gain reuse (above): without `keep` no snapshot is written and nothing outlives the call
     a.fac = reuse_fit ? h->fac : nullptr;
     a.snap = keep ? h->snap : nullptr;

@@ -151,10 +151,11 @@ __device__ __forceinline__ void bw4_ops_each(BW4Ops& o, FN&& fn) {
     for (int I = 0; I < 3; ++I) fn(o.S[K][I], i++);
 }
 
-template <int MODE, int KAUX>
+template <int MODE, int KAUX, bool TRK>
 __device__ __forceinline__ unsigned lq_backward4_body(const BW4Ops& op, int b0, int B,
                                                       unsigned active, int T, const double* __restrict__ x,
                                                       const double* __restrict__ u,
+                                                      const double* __restrict__ xtraj,
                                                       double* __restrict__ d_out, double* __restrict__ K_out,
                                                       double* __restrict__ fac, double mu,
                                                       double* lds ILQR_EDGE_PARAM);
@@ -164,10 +165,10 @@ __device__ __forceinline__ unsigned lq_backward4_body(const BW4Ops& op, int b0, 
 // reused the stored gains in this launch, 0 if it ran the full recursion (one store per
 // wave; nullptr: not recorded). KAUX: the cache-policy word of the vector-only mode's K and
 // factor loads (buf_ld).
-template <int MODE, int KAUX = 0>
+template <int MODE, int KAUX = 0, bool TRK = false>
 __device__ unsigned lq_backward4_wave(const LQParams& P, int b0, int B, unsigned active, int T,
                                       const double* __restrict__ x, const double* __restrict__ u,
-                                      double* __restrict__ d_out, double* __restrict__ K_out,
+                                      const double* __restrict__ xtraj, double* __restrict__ d_out, double* __restrict__ K_out,
                                       double* __restrict__ fac, double mu, double* lds,
                                       double* __restrict__ snap = nullptr,
                                       int32_t* __restrict__ rec = nullptr ILQR_EDGE_PARAM_DEF) {
@@ -215,18 +216,19 @@ __device__ unsigned lq_backward4_wave(const LQParams& P, int b0, int B, unsigned
     }
     if (rec && l == 0) rec[b0 / BW4_SLOTS] = same ? 1 : 0;
     if (same)
-      return lq_backward4_body<BW4_VEC, KAUX>(op, b0, B, active, T, x, u, d_out, K_out, fac, mu, lds ILQR_EDGE_PASS);
+      return lq_backward4_body<BW4_VEC, KAUX, TRK>(op, b0, B, active, T, x, u, xtraj, d_out, K_out, fac, mu, lds ILQR_EDGE_PASS);
     if (sw) bw4_ops_each(op, [&](double& v, int i) { sw[i * 64] = __builtin_bit_cast(unsigned long long, v); });
-    return lq_backward4_body<BW4_STORE, 0>(op, b0, B, active, T, x, u, d_out, K_out, fac, mu, lds ILQR_EDGE_PASS);
+    return lq_backward4_body<BW4_STORE, 0, TRK>(op, b0, B, active, T, x, u, xtraj, d_out, K_out, fac, mu, lds ILQR_EDGE_PASS);
   } else {
-    return lq_backward4_body<MODE, KAUX>(op, b0, B, active, T, x, u, d_out, K_out, fac, mu, lds ILQR_EDGE_PASS);
+    return lq_backward4_body<MODE, KAUX, TRK>(op, b0, B, active, T, x, u, xtraj, d_out, K_out, fac, mu, lds ILQR_EDGE_PASS);
   }
 }
 
-template <int MODE, int KAUX>
+template <int MODE, int KAUX, bool TRK>
 __device__ __forceinline__ unsigned lq_backward4_body(const BW4Ops& op, int b0, int B,
                                                       unsigned active, int T, const double* __restrict__ x,
                                                       const double* __restrict__ u,
+                                                      const double* __restrict__ xtraj,
                                                       double* __restrict__ d_out, double* __restrict__ K_out,
                                                       double* __restrict__ fac, double mu,
                                                       double* lds ILQR_EDGE_PARAM) {
@@ -327,10 +329,29 @@ __device__ __forceinline__ unsigned lq_backward4_body(const BW4Ops& op, int b0, 
     for (int K = 0; K < 3; ++K) z[K] = buf_ld(rX, xo + 32 * K, 0);
     z[3] = buf_ld(rU, uo, 0);
   };
+  // Tracking (TRK, ILQR_TRACK_CONSISTENT): the cost the forward measures is
+  // ℓ(x_t − x_traj_t, u_t) for t < T, so lx_t = (Q + Qᵀ)(x_t − x_traj_t): z's x blocks take
+  // the reference's rows off (rq, rqn beside zq, zqn), loaded with them through a resource of
+  // their own at the same per-lane offsets (slots past nslot read 0, step 0 clamped alike)
+  // and subtracted where L z is formed, so the loads stay as far ahead as x's. Row T of
+  // x_traj is never read (the terminal cost is on the raw x_N, above).
+  [[maybe_unused]] double rq[3], rqn[3];
+  [[maybe_unused]] auto load_rq = [&](double (&r)[3], int t0) {
+    const auto rXT = buffer_rsrc(const_cast<double*>(xtraj) + (size_t)b0 * (T + 1) * NX,
+                                 (uint32_t)(nslot * (T + 1) * NX * 8));
+    const int tz = t0 - kap > 0 ? t0 - kap : 0;
+    const uint32_t xo = (uint32_t)(((beta * (T + 1) + tz) * NX + rho) * 8);
+#pragma unroll
+    for (int K = 0; K < 3; ++K) r[K] = buf_ld(rXT, xo + 32 * K, 0);
+  };
   // L z for the four steps from t0 (column κ = step t0 − κ), from zq; then the next
   // four steps' z. Computed one step ahead of its first use, so each step's column
   // permutes can issue at the top of the step, behind the S·F MFMAs.
   auto lz_block = [&](int t0) {
+    if constexpr (TRK) {
+#pragma unroll
+      for (int K = 0; K < 3; ++K) zq[K] -= rq[K];
+    }
 #pragma unroll
     for (int I = 0; I < 3; ++I) {
       double v = 0.0;
@@ -342,13 +363,23 @@ __device__ __forceinline__ unsigned lq_backward4_body(const BW4Ops& op, int b0, 
     if constexpr (VEC) {
 #pragma unroll
       for (int K = 0; K < 4; ++K) zq[K] = zqn[K];
+      if constexpr (TRK) {
+#pragma unroll
+        for (int K = 0; K < 3; ++K) rq[K] = rqn[K];
+      }
       load_zq(zqn, t0 - 8);
+      if constexpr (TRK) load_rq(rqn, t0 - 8);
     } else {
       load_zq(zq, t0 - 4);
+      if constexpr (TRK) load_rq(rq, t0 - 4);
     }
   };
   load_zq(zq, T - 1);
   if constexpr (VEC) load_zq(zqn, T - 5);
+  if constexpr (TRK) {
+    load_rq(rq, T - 1);
+    if constexpr (VEC) load_rq(rqn, T - 5);
+  }
 
   double* Hl = lds + beta * 16;
   double Klast[4];
@@ -571,6 +602,8 @@ __device__ __forceinline__ unsigned lq_backward4_body(const BW4Ops& op, int b0, 
   return r;
 }
 
+// The tracking instantiations (ILQR_TRACK_CONSISTENT with an x_traj; TRK here and below) are
+// kernels of their own names beside the plain ones, which stay as they were.
 __global__ __launch_bounds__(256) void lq_backward4_kernel(LQParams P, int B, int T,
                                                            const double* __restrict__ x,
                                                            const double* __restrict__ u,
@@ -581,16 +614,34 @@ __global__ __launch_bounds__(256) void lq_backward4_kernel(LQParams P, int B, in
   const int w = threadIdx.x >> 6;
   const int b0 = (blockIdx.x * BW4_WAVES + w) * BW4_SLOTS;
   if (b0 >= B) return;
-  const unsigned nan = lq_backward4_wave<BW4_FULL>(P, b0, B, 0xFu, T, x, u, d, K, nullptr, mu, lds + w * BW4_LDS);
+  const unsigned nan = lq_backward4_wave<BW4_FULL>(P, b0, B, 0xFu, T, x, u, nullptr, d, K, nullptr, mu, lds + w * BW4_LDS);
+  const int l = threadIdx.x & 63;
+  if (status && l < BW4_SLOTS && b0 + l < B) status[b0 + l] = ((nan >> l) & 1u) ? ILQR_TRAJ_NAN : ILQR_TRAJ_OK;
+}
+
+// ilqr_backward_tracking: lx_t = (Q + Qᵀ)(x_t − x_traj_t)
+__global__ __launch_bounds__(256) void lq_backward4_track_kernel(LQParams P, int B, int T,
+                                                                 const double* __restrict__ x,
+                                                                 const double* __restrict__ u,
+                                                                 const double* __restrict__ xtraj,
+                                                                 double* __restrict__ d,
+                                                                 double* __restrict__ K,
+                                                                 int32_t* __restrict__ status, double mu) {
+  __shared__ __attribute__((aligned(16))) double lds[BW4_WAVES * BW4_LDS];
+  const int w = threadIdx.x >> 6;
+  const int b0 = (blockIdx.x * BW4_WAVES + w) * BW4_SLOTS;
+  if (b0 >= B) return;
+  const unsigned nan =
+      lq_backward4_wave<BW4_FULL, 0, true>(P, b0, B, 0xFu, T, x, u, xtraj, d, K, nullptr, mu, lds + w * BW4_LDS);
   const int l = threadIdx.x & 63;
   if (status && l < BW4_SLOTS && b0 + l < B) status[b0 + l] = ((nan >> l) & 1u) ? ILQR_TRAJ_NAN : ILQR_TRAJ_OK;
 }
 
 // fit iteration, part 1 (see lq_iter_backward_kernel): slots whose status is not OK
 // are skipped (computed on, never stored)
-__global__ __launch_bounds__(256) void lq_iter_backward4_kernel(LQParams P, int B, int T, IterArgs a,
-                                                                double mu) {
-  __shared__ __attribute__((aligned(16))) double lds[BW4_WAVES * BW4_LDS];
+template <bool TRK>
+__device__ __forceinline__ void lq_iter_backward4_entry(const LQParams& P, int B, int T, const IterArgs& a,
+                                                        double mu, double* lds) {
   const int w = threadIdx.x >> 6;
   const int b0 = (blockIdx.x * BW4_WAVES + w) * BW4_SLOTS;
   if (b0 >= B) return;
@@ -599,12 +650,26 @@ __global__ __launch_bounds__(256) void lq_iter_backward4_kernel(LQParams P, int 
   for (int q = 0; q < BW4_SLOTS; ++q)
     if (b0 + q < B && a.status[b0 + q] == ILQR_TRAJ_OK) active |= 1u << q;
   if (active == 0) return;
-  const unsigned nan = lq_backward4_wave<BW4_FULL>(P, b0, B, active, T, a.x, a.u, a.d, a.K, nullptr, mu, lds + w * BW4_LDS) & active;
+  const unsigned nan = lq_backward4_wave<BW4_FULL, 0, TRK>(P, b0, B, active, T, a.x, a.u, a.xtraj, a.d, a.K, nullptr,
+                                                           mu, lds + w * BW4_LDS) &
+                       active;
   const int l = threadIdx.x & 63;
   if (l < BW4_SLOTS && ((nan >> l) & 1u)) {
     a.status[b0 + l] = ILQR_TRAJ_NAN;  // reference: AssertionError at backward_pass.jl:353
     if (a.res_parity) a.res_parity[b0 + l] = a.parity;
   }
+}
+
+__global__ __launch_bounds__(256) void lq_iter_backward4_kernel(LQParams P, int B, int T, IterArgs a,
+                                                                double mu) {
+  __shared__ __attribute__((aligned(16))) double lds[BW4_WAVES * BW4_LDS];
+  lq_iter_backward4_entry<false>(P, B, T, a, mu, lds);
+}
+
+__global__ __launch_bounds__(256) void lq_iter_backward4_track_kernel(LQParams P, int B, int T, IterArgs a,
+                                                                      double mu) {
+  __shared__ __attribute__((aligned(16))) double lds[BW4_WAVES * BW4_LDS];
+  lq_iter_backward4_entry<true>(P, B, T, a, mu, lds);
 }
 
 // One fit iteration (forward_pass.jl:162-175) in ONE launch: each wave runs the
@@ -625,7 +690,7 @@ constexpr int FUSED_LDS = PIPE_R * RING_SLOT + RING_LAREA;  // doubles per wave
 // holds an earlier fit's gains for the same μ (each wave then takes BW4_VEC or BW4_STORE by
 // its operand snapshot), BW4_FULL otherwise. One kernel name per mode (below), so a kernel
 // trace tells them apart.
-template <bool MF, int BW>
+template <bool MF, int BW, bool TRK>
 __device__ __forceinline__ void lq_iter_fused4(const LQParams& P, int B, int T, const IterArgs& a,
                                                const LSParams& ls, double* lds_all) {
   static_assert(FUSED_LDS >= BW4_LDS, "backward scratch fits the ring");
@@ -683,7 +748,7 @@ __device__ __forceinline__ void lq_iter_fused4(const LQParams& P, int B, int T, 
   }
   if (active != 0) {
     const unsigned nan =
-        lq_backward4_wave<BW, BW_KAUX>(P, b0, B, active, T, a.x, a.u, a.d, a.K, a.fac, ls.mu, lds, a.snap,
+        lq_backward4_wave<BW, BW_KAUX, TRK>(P, b0, B, active, T, a.x, a.u, a.xtraj, a.d, a.K, a.fac, ls.mu, lds, a.snap,
                                        a.branch ILQR_EDGE_PASS) &
         active;
     if (owner && ((nan >> q) & 1u)) {
@@ -717,17 +782,22 @@ __device__ __forceinline__ void lq_iter_fused4(const LQParams& P, int B, int T, 
 #endif
 }
 
-#define ILQR_FUSED4_KERNEL(NAME, BW)                                                                  \
+#define ILQR_FUSED4_KERNEL(NAME, BW, TRK)                                                             \
   template <bool MF>                                                                                  \
   __global__ __launch_bounds__(64 * FUSED_WAVES) void NAME(LQParams P, int B, int T, IterArgs a,     \
                                                            LSParams ls) {                             \
     __shared__ __attribute__((aligned(16))) double lds_all[FUSED_WAVES * FUSED_LDS];                  \
-    lq_iter_fused4<MF, BW>(P, B, T, a, ls, lds_all);                                                  \
+    lq_iter_fused4<MF, BW, TRK>(P, B, T, a, ls, lds_all);                                             \
   }
-ILQR_FUSED4_KERNEL(lq_iter_fused4_kernel, BW4_FULL)
-ILQR_FUSED4_KERNEL(lq_iter_fused4_store_kernel, BW4_STORE)
-ILQR_FUSED4_KERNEL(lq_iter_fused4_vec_kernel, BW4_VEC)
-ILQR_FUSED4_KERNEL(lq_iter_fused4_check_kernel, BW4_CHECK)
+ILQR_FUSED4_KERNEL(lq_iter_fused4_kernel, BW4_FULL, false)
+ILQR_FUSED4_KERNEL(lq_iter_fused4_store_kernel, BW4_STORE, false)
+ILQR_FUSED4_KERNEL(lq_iter_fused4_vec_kernel, BW4_VEC, false)
+ILQR_FUSED4_KERNEL(lq_iter_fused4_check_kernel, BW4_CHECK, false)
+// the same four with the tracking backward (a.track with an a.xtraj)
+ILQR_FUSED4_KERNEL(lq_iter_fused4_track_kernel, BW4_FULL, true)
+ILQR_FUSED4_KERNEL(lq_iter_fused4_track_store_kernel, BW4_STORE, true)
+ILQR_FUSED4_KERNEL(lq_iter_fused4_track_vec_kernel, BW4_VEC, true)
+ILQR_FUSED4_KERNEL(lq_iter_fused4_track_check_kernel, BW4_CHECK, true)
 #undef ILQR_FUSED4_KERNEL
 
 }  // namespace
@@ -743,7 +813,19 @@ hipError_t launch_lq_iter_fused4(const LQParams& p, int B, int T, const IterArgs
   const int grid = (B + per_wg - 1) / per_wg;
   auto go = [&](auto kernel) { kernel<<<grid, 64 * FUSED_WAVES, 0, s>>>(p, B, T, a, ls); };
   const int bw = vec ? BW4_VEC : (check ? BW4_CHECK : (a.fac ? BW4_STORE : BW4_FULL));
-  if (mfma) {
+  if (lq_tracks(a)) {
+    if (mfma) {
+      if (bw == BW4_VEC) go(lq_iter_fused4_track_vec_kernel<true>);
+      else if (bw == BW4_CHECK) go(lq_iter_fused4_track_check_kernel<true>);
+      else if (bw == BW4_STORE) go(lq_iter_fused4_track_store_kernel<true>);
+      else go(lq_iter_fused4_track_kernel<true>);
+    } else {
+      if (bw == BW4_VEC) go(lq_iter_fused4_track_vec_kernel<false>);
+      else if (bw == BW4_CHECK) go(lq_iter_fused4_track_check_kernel<false>);
+      else if (bw == BW4_STORE) go(lq_iter_fused4_track_store_kernel<false>);
+      else go(lq_iter_fused4_track_kernel<false>);
+    }
+  } else if (mfma) {
     if (bw == BW4_VEC) go(lq_iter_fused4_vec_kernel<true>);
     else if (bw == BW4_CHECK) go(lq_iter_fused4_check_kernel<true>);
     else if (bw == BW4_STORE) go(lq_iter_fused4_store_kernel<true>);
@@ -763,16 +845,19 @@ int bw4_grid(int B) {
 }
 
 hipError_t launch_lq_backward4(const LQParams& p, int B, int T, const double* x, const double* u,
-                               double* d, double* K, int32_t* status, double mu, hipStream_t s) {
+                               double* d, double* K, int32_t* status, double mu, hipStream_t s,
+                               const double* xtraj) {
   if (B <= 0) return hipSuccess;
-  lq_backward4_kernel<<<bw4_grid(B), 256, 0, s>>>(p, B, T, x, u, d, K, status, mu);
+  if (xtraj) lq_backward4_track_kernel<<<bw4_grid(B), 256, 0, s>>>(p, B, T, x, u, xtraj, d, K, status, mu);
+  else lq_backward4_kernel<<<bw4_grid(B), 256, 0, s>>>(p, B, T, x, u, d, K, status, mu);
   return hipGetLastError();
 }
 
 hipError_t launch_lq_iter_backward4(const LQParams& p, int B, int T, const IterArgs& a, double mu,
                                     hipStream_t s) {
   if (B <= 0) return hipSuccess;
-  lq_iter_backward4_kernel<<<bw4_grid(B), 256, 0, s>>>(p, B, T, a, mu);
+  if (lq_tracks(a)) lq_iter_backward4_track_kernel<<<bw4_grid(B), 256, 0, s>>>(p, B, T, a, mu);
+  else lq_iter_backward4_kernel<<<bw4_grid(B), 256, 0, s>>>(p, B, T, a, mu);
   return hipGetLastError();
 }
 

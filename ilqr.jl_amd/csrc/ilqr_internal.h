@@ -98,6 +98,10 @@ struct IterArgs {
   int iter;             // 1-based iteration index (fit)
   int init;             // fit's first iteration on the fused LQ kernel: the kernel itself sets
                         // prev_cost = Inf, status OK, res_parity = input, iters = 0 (fit_init)
+  int track;            // LQ family, host side only (no kernel reads it): the backward differentiates
+                        // the tracking cost, lx_t = (Q + Qᵀ)(x_t − x_traj_t) (ILQR_TRACK_CONSISTENT);
+                        // the launchers then pick the tracking kernels (lq_tracks). It sits in
+                        // the padding before `coop`: every other member keeps its offset
   const LSCoop* coop;   // the fused LQ kernel's cooperative line search (device memory, one
                         // per handle; read only when the search starts, so its pointers
                         // hold no SGPRs through the backward pass); nullptr: off
@@ -106,15 +110,23 @@ struct IterArgs {
                         // of its own work is ONE load (no dependent load of *coop first)
 };
 
+// the LQ launch of `a` runs the tracking backward: the mode is on and there is a reference
+// (x_traj == nullptr means zeros, where tracking is the plain recursion: the plain kernels)
+static_assert(sizeof(IterArgs) == 176 && offsetof(IterArgs, coop) == 152, "IterArgs::track fills padding");
+inline bool lq_tracks(const IterArgs& a) { return a.track != 0 && a.xtraj != nullptr; }
+
 // Returns hipSuccess or the launch error. All launches are asynchronous on `s`.
+// `xtraj` (the launch_lq_backward* family): nullptr the plain backward, else backward_pass of
+// the tracking cost (ilqr_backward_tracking)
 hipError_t launch_lq_backward(int nx, int nu, const LQParams& p, int B, int T, const double* x,
                               const double* u, double* d, double* K, int32_t* status, double mu,
-                              hipStream_t s, bool wave = false);
+                              hipStream_t s, bool wave = false, const double* xtraj = nullptr);
 // (12, 4) goes to the four-trajectories-per-wave kernel (ilqr_bw4.hip) unless
 // `wave` (ILQR_SCHED_BACKWARD_WAVE) selects the one-trajectory-per-wave kernel
 // (launch_lq_backward_v6), which the pipelined schedule's fused kernel also runs.
 hipError_t launch_lq_backward4(const LQParams& p, int B, int T, const double* x, const double* u,
-                               double* d, double* K, int32_t* status, double mu, hipStream_t s);
+                               double* d, double* K, int32_t* status, double mu, hipStream_t s,
+                               const double* xtraj = nullptr);
 hipError_t launch_lq_iter_backward4(const LQParams& p, int B, int T, const IterArgs& a, double mu,
                                     hipStream_t s);
 // backward (four trajectories per wave) + LDS-ring forward of one fit iteration in one
@@ -132,7 +144,7 @@ inline size_t lq_fused_waves(size_t B) { return (B + 3) / 4; }
 inline size_t lq_snap_doubles(size_t B) { return lq_fused_waves(B) * 31 * 64; }
 hipError_t launch_lq_backward_v6(int nx, int nu, const LQParams& p, int B, int T, const double* x,
                                  const double* u, double* d, double* K, int32_t* status, double mu,
-                                 hipStream_t s);
+                                 hipStream_t s, const double* xtraj = nullptr);
 hipError_t launch_lq_forward(int nx, int nu, const LQParams& p, int B, int T, const double* x,
                              const double* u, const double* xtraj, const double* d,
                              const double* K, const double* prev_cost, double* xnew,

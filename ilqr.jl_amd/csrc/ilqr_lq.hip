@@ -48,10 +48,21 @@ namespace {
 // Newton steps per reciprocal, other symmetrisation periods, the round-1 gradient and
 // gain stores — and tools/ablate_bw.hip's ablation bits live in
 // tools/ablation/restore_alternates.patch)
-template <int NX, int NU>
+// TRK (ILQR_TRACK_CONSISTENT with an x_traj): the gradient of the cost the forward measures,
+// lx_t = (Q + Qᵀ)(x_t − x_traj_t) for t < T: the x rows of z take x_traj_t's off. The
+// terminal s = S x_N stays on the raw x_N (total_cost :192); row T of x_traj is never read.
+// The reference comes as a last argument that is empty in the plain instantiation, whose
+// callers and code are then what they were.
+template <bool TRK>
+struct TrackRef {};
+template <>
+struct TrackRef<true> {
+  const double* xtraj;  // (B, T+1, NX)
+};
+template <int NX, int NU, bool TRK = false>
 __device__ bool lq_backward_wave(const LQParams& P, int b, int T, const double* __restrict__ x,
                                  const double* __restrict__ u, double* __restrict__ d_out,
-                                 double* __restrict__ K_out, double mu, double* lds) {
+                                 double* __restrict__ K_out, double mu, double* lds, TrackRef<TRK> ref = {}) {
   static_assert(NX + NU <= 16 && NX < 16 && NU <= 4, "MFMA tile mapping needs nx+nu <= 16, nu <= 4");
   constexpr int KS = (NX + 3) / 4;  // k-steps of 4 over the state dimension
   constexpr int SROW = NX;          // row/column of Sp holding s
@@ -150,7 +161,24 @@ __device__ bool lq_backward_wave(const LQParams& P, int b, int T, const double* 
     }
     return z;
   };
+  // x_traj_t at the x rows (KS registers: rows q+4r ≥ 4·KS hold no state), loaded with z one
+  // step ahead and subtracted where L z is formed, so its latency hides as z's does
+  [[maybe_unused]] auto load_r = [&](int t) {
+    d4 r = {0.0, 0.0, 0.0, 0.0};
+    if constexpr (TRK) {
+      const double* rt = ref.xtraj + ((size_t)b * (T + 1) + t) * NX;
+#pragma unroll
+      for (int k = 0; k < KS; ++k) {
+        const int i = q + 4 * k;
+        const double v = rt[i < NX ? i : 0];
+        r[k] = i < NX ? v : 0.0;
+      }
+    }
+    return r;
+  };
   d4 zc = load_z(T - 1);
+  d4 rc = {0.0, 0.0, 0.0, 0.0};
+  if constexpr (TRK) rc = load_r(T - 1);
   double* Kb = K_out + (size_t)b * T * NU * NX;
   double* db = d_out + (size_t)b * T * NU;
   // gains go out through raw buffer stores (inactive lanes dropped, no exec branch)
@@ -160,6 +188,8 @@ __device__ bool lq_backward_wave(const LQParams& P, int b, int T, const double* 
 
   for (int t = T - 1; t >= 0; --t) {
     const d4 zn = load_z(t > 0 ? t - 1 : 0);
+    d4 rn = {0.0, 0.0, 0.0, 0.0};
+    if constexpr (TRK) rn = load_r(t > 0 ? t - 1 : 0);
 
     // Y = Sp · F (optimal_controller_param's S'A, S'B and the row sᵀF)
     // Z = L + Fᵀ Y = [[lxx + AᵀSA, AᵀSB], [BᵀSA, luu + BᵀSB]]  (:182-183, first terms of :270)
@@ -176,7 +206,7 @@ __device__ bool lq_backward_wave(const LQParams& P, int b, int T, const double* 
     // publishes g (the other lanes write a junk LDS row), so no reduction waits on Y.
     double part = 0.0;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) part = fma(Lc[r], zc[r], part);
+    for (int r = 0; r < 4; ++r) part = fma(Lc[r], (TRK && r < KS) ? zc[r] - rc[r] : zc[r], part);
     const double gq = colsum4(part) + Y[SROW / 4];  // exact in lane q = SROW%4
 
     // hand the NU rows [G | H] and g to every lane
@@ -222,6 +252,7 @@ __device__ bool lq_backward_wave(const LQParams& P, int b, int T, const double* 
     }
     Sp = mfma(-kq, wk, Cin);
     zc = zn;
+    if constexpr (TRK) rc = rn;
 
     // S ← (S + Sᵀ)/2 on the state block (the identity in exact arithmetic). The
     // accumulator tile feeds the next Y MFMA as its own transpose, so rounding
@@ -390,6 +421,23 @@ __global__ __launch_bounds__(256, 4) void lq_backward_kernel(LQParams P, int B, 
   if (status && (threadIdx.x & 63) == 0) status[b] = nan ? ILQR_TRAJ_NAN : ILQR_TRAJ_OK;
 }
 
+// ilqr_backward_tracking: lx_t = (Q + Qᵀ)(x_t − x_traj_t)
+template <int NX, int NU>
+__global__ __launch_bounds__(256, 4) void lq_backward_track_kernel(LQParams P, int B, int T,
+                                                                const double* __restrict__ x,
+                                                                const double* __restrict__ u,
+                                                                const double* __restrict__ xtraj,
+                                                                double* __restrict__ d,
+                                                                double* __restrict__ K,
+                                                                int32_t* __restrict__ status, double mu) {
+  __shared__ __attribute__((aligned(16))) double lds[WAVES_PER_WG * BW_LDS];
+  const int w = threadIdx.x >> 6;
+  const int b = blockIdx.x * WAVES_PER_WG + w;
+  if (b >= B) return;
+  const bool nan = lq_backward_wave<NX, NU, true>(P, b, T, x, u, d, K, mu, lds + w * BW_LDS, {xtraj});
+  if (status && (threadIdx.x & 63) == 0) status[b] = nan ? ILQR_TRAJ_NAN : ILQR_TRAJ_OK;
+}
+
 template <int NX, int NU>
 __global__ __launch_bounds__(64) void lq_forward_kernel(
     LQParams P, int B, int T, const double* __restrict__ x, const double* __restrict__ u,
@@ -419,14 +467,16 @@ __global__ __launch_bounds__(64) void lq_forward_kernel(
 
 // One fit iteration (forward_pass.jl:161-176), part 1: backward_pass for every
 // trajectory whose status is OK (4 waves / workgroup, one trajectory per wave).
-template <int NX, int NU>
+template <int NX, int NU, bool TRK = false>
 __global__ __launch_bounds__(256, 4) void lq_iter_backward_kernel(LQParams P, int B, int T, IterArgs a,
                                                                double mu) {
   __shared__ __attribute__((aligned(16))) double lds[WAVES_PER_WG * BW_LDS];
   const int w = threadIdx.x >> 6;
   const int b = blockIdx.x * WAVES_PER_WG + w;
   if (b >= B || a.status[b] != ILQR_TRAJ_OK) return;
-  const bool nan = lq_backward_wave<NX, NU>(P, b, T, a.x, a.u, a.d, a.K, mu, lds + w * BW_LDS);
+  bool nan;
+  if constexpr (TRK) nan = lq_backward_wave<NX, NU, true>(P, b, T, a.x, a.u, a.d, a.K, mu, lds + w * BW_LDS, {a.xtraj});
+  else nan = lq_backward_wave<NX, NU>(P, b, T, a.x, a.u, a.d, a.K, mu, lds + w * BW_LDS);
   if (nan && (threadIdx.x & 63) == 0) {
     a.status[b] = ILQR_TRAJ_NAN;  // reference: AssertionError at backward_pass.jl:353
     if (a.res_parity) a.res_parity[b] = a.parity;
@@ -549,7 +599,7 @@ __global__ __launch_bounds__(64 * FW_WAVES) void lq_iter_forward_ring_kernel(LQP
   }
 }
 
-template <int NX, int NU>
+template <int NX, int NU, bool TRK = false>
 __global__ __launch_bounds__(256, 4) void lq_iter_pipe_kernel(LQParams P, int B, int T,
                                                               IterArgs cur, IterArgs prev,
                                                               LSParams ls, int flags) {
@@ -563,7 +613,11 @@ __global__ __launch_bounds__(256, 4) void lq_iter_pipe_kernel(LQParams P, int B,
   auto backward = [&](const IterArgs& a) {
     const int b = b0 + w;
     if (b < B && a.status[b] == ILQR_TRAJ_OK) {
-      const bool nan = lq_backward_wave<NX, NU>(P, b, T, a.x, a.u, a.d, a.K, ls.mu, lds + w * BW_LDS);
+      bool nan;
+      if constexpr (TRK)
+        nan = lq_backward_wave<NX, NU, true>(P, b, T, a.x, a.u, a.d, a.K, ls.mu, lds + w * BW_LDS, {a.xtraj});
+      else
+        nan = lq_backward_wave<NX, NU>(P, b, T, a.x, a.u, a.d, a.K, ls.mu, lds + w * BW_LDS);
       if (nan && (threadIdx.x & 63) == 0) {
         a.status[b] = ILQR_TRAJ_NAN;  // reference: AssertionError at backward_pass.jl:353
         if (a.res_parity) a.res_parity[b] = a.parity;
@@ -775,16 +829,18 @@ bool lq_supported(int nx, int nu) { return nx == 12 && nu == 4; }
 
 hipError_t launch_lq_backward(int nx, int nu, const LQParams& p, int B, int T, const double* x,
                               const double* u, double* d, double* K, int32_t* status, double mu,
-                              hipStream_t s, bool wave) {
-  if (wave) return launch_lq_backward_v6(nx, nu, p, B, T, x, u, d, K, status, mu, s);
-  if (nx == 12 && nu == 4) return launch_lq_backward4(p, B, T, x, u, d, K, status, mu, s);
+                              hipStream_t s, bool wave, const double* xtraj) {
+  if (wave) return launch_lq_backward_v6(nx, nu, p, B, T, x, u, d, K, status, mu, s, xtraj);
+  if (nx == 12 && nu == 4) return launch_lq_backward4(p, B, T, x, u, d, K, status, mu, s, xtraj);
   return hipErrorInvalidValue;
 }
 
 hipError_t launch_lq_backward_v6(int nx, int nu, const LQParams& p, int B, int T, const double* x,
                                  const double* u, double* d, double* K, int32_t* status, double mu,
-                                 hipStream_t s) {
+                                 hipStream_t s, const double* xtraj) {
   const int grid = (B + WAVES_PER_WG - 1) / WAVES_PER_WG;
+  if (xtraj)
+    ILQR_DISPATCH(12, 4, (lq_backward_track_kernel<NX_, NU_><<<grid, 256, 0, s>>>(p, B, T, x, u, xtraj, d, K, status, mu)));
   ILQR_DISPATCH(12, 4, (lq_backward_kernel<NX_, NU_><<<grid, 256, 0, s>>>(p, B, T, x, u, d, K, status, mu)));
   return hipErrorInvalidValue;
 }
@@ -841,6 +897,8 @@ hipError_t launch_lq_iter_backward(int nx, int nu, const LQParams& p, int b0, in
   const IterArgs as = shift(a, nx, nu, T, b0);
   if (wave) {
     const int grid = (B + WAVES_PER_WG - 1) / WAVES_PER_WG;
+    if (lq_tracks(as))
+      ILQR_DISPATCH(12, 4, (lq_iter_backward_kernel<NX_, NU_, true><<<grid, 256, 0, s>>>(ps, B, T, as, mu)));
     ILQR_DISPATCH(12, 4, (lq_iter_backward_kernel<NX_, NU_><<<grid, 256, 0, s>>>(ps, B, T, as, mu)));
     return hipErrorInvalidValue;
   }
@@ -868,6 +926,9 @@ hipError_t launch_lq_iter_pipe(int nx, int nu, const LQParams& p, int B, int T, 
                                const IterArgs& prev, const LSParams& ls, int flags, hipStream_t s) {
   if (B <= 0) return hipSuccess;
   const int grid = (B + WAVES_PER_WG - 1) / WAVES_PER_WG;
+  // (`cur` and `prev` are one fit's: the same mode and reference)
+  if (lq_tracks(cur))
+    ILQR_DISPATCH(12, 4, (lq_iter_pipe_kernel<NX_, NU_, true><<<grid, 256, 0, s>>>(p, B, T, cur, prev, ls, flags)));
   ILQR_DISPATCH(12, 4, (lq_iter_pipe_kernel<NX_, NU_><<<grid, 256, 0, s>>>(p, B, T, cur, prev, ls, flags)));
   return hipErrorInvalidValue;
 }

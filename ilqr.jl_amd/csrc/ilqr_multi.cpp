@@ -242,6 +242,16 @@ ilqr_status ilqr_multi_set_schedule(ilqr_multi* m, int flags) {
   return ILQR_OK;
 }
 
+ilqr_status ilqr_multi_set_tracking(ilqr_multi* m, int32_t mode) {
+  if (!m || (mode != ILQR_TRACK_FORWARD_ONLY && mode != ILQR_TRACK_CONSISTENT)) return ILQR_ERR_BAD_ARG;
+  for (Shard& s : m->shards)
+    if (s.h) {
+      const ilqr_status st = ilqr_set_tracking(s.h, mode);
+      if (st != ILQR_OK) return st;
+    }
+  return ILQR_OK;
+}
+
 ilqr_status ilqr_multi_set_problem(ilqr_multi* m, const ilqr_problem* host_problem) {
   if (!m) return ILQR_ERR_BAD_ARG;
   ilqr_status st = check_problem(m, host_problem);

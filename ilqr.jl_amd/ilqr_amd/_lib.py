@@ -42,6 +42,8 @@ SCHED_FORWARD_MFMA = 32
 SCHED_SEQUENTIAL_SEARCH = 64
 SCHED_FULL_BACKWARD = 128
 SCHED_REUSE_PER_CALL = 256
+TRACK_FORWARD_ONLY = 0   # ilqr_set_tracking: the reference's behaviour (backward ignores x_traj)
+TRACK_CONSISTENT = 1     # the backward differentiates the tracking cost the forward measures
 MULTI_WARM_START = 1
 MULTI_USE_X_TRAJ = 2
 
@@ -130,6 +132,10 @@ SIGNATURES = {
     "ilqr_sync": (C.c_int, [P]),
     "ilqr_set_schedule": (C.c_int, [P, C.c_int]),
     "ilqr_reuse_record": (C.c_int, [P, P, C.c_int32, C.POINTER(C.c_int32)]),
+    "ilqr_set_tracking": (C.c_int, [P, C.c_int32]),
+    "ilqr_get_tracking": (C.c_int32, [P]),
+    "ilqr_backward_tracking": (C.c_int, [P, C.POINTER(Problem), C.POINTER(Options), P, P, P, P, P, P]),
+    "ilqr_multi_set_tracking": (C.c_int, [P, C.c_int32]),
     "ilqr_multi_create": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "ilqr_multi_destroy": (C.c_int, [P]),
     "ilqr_multi_set_schedule": (C.c_int, [P, C.c_int]),

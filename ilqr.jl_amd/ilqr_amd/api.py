@@ -241,15 +241,24 @@ def forward_pass(x, u, x_traj, du, K, prev_cost, dynamicsf, immediate_cost, fina
 
 
 def fit(x_init, u_init, dynamicsf, immediate_cost, final_cost, *, x_traj=None,
-        max_iter: int = 100, tol: float = 1e-6, return_info: bool = False, verbose: bool = False):
+        max_iter: int = 100, tol: float = 1e-6, return_info: bool = False, verbose: bool = False,
+        track: bool = False):
     """→ (x̄, ū) exactly like iLQR.fit (forward_pass.jl:148-179), including its
     quirk of returning the iterate BEFORE the update that met `tol` (:171).
     verbose: print the reference's per-iteration line `Iteration: i  Total Cost: c`
     (:167) — for each trajectory of a batch — from the fit's history (ilqr_fit_ex);
     return_info adds it as info["history"] (arrays (max_iter, batch): cost, trials,
-    alpha, du2)."""
+    alpha, du2).
+    track: the backward pass differentiates the tracking cost the forward pass measures,
+    lx_t = (Q + Qᵀ)(x_t − x_traj_t) for t < T (ilqr_set_tracking; the end state is still
+    measured raw). Off (the default) is the reference's behaviour: backward_pass ignores
+    x_traj. The LQ family only."""
     if not isinstance(max_iter, (int, np.integer)) or isinstance(max_iter, bool):
         raise TypeError("max_iter::Int64")   # forward_pass.jl:152
+    if track and _family(dynamicsf, immediate_cost, final_cost) != "lq":
+        raise NotImplementedError("track=True is implemented for the LQ family only (LinearDynamics, "
+                                  "QuadraticCost, QuadraticFinalCost); the other families' backward "
+                                  "passes ignore x_traj as the reference's does")
     xb, batched, is_t = _as_batch(x_init, "x_init", 2)
     ub, _, _ = _as_batch(u_init, "u_init", 2)
     nb, N, nx = xb.shape
@@ -273,9 +282,14 @@ def fit(x_init, u_init, dynamicsf, immediate_cost, final_cost, *, x_traj=None,
         s.close()
     else:
         s = _solver(xb, ub, dynamicsf, immediate_cost, final_cost)
-        r = s.fit(xb, ub, x_traj=xt, max_iter=int(max_iter), tol=float(tol),
-                  history=verbose or return_info)
-        s.close()
+        try:
+            s.set_tracking(bool(track))
+            r = s.fit(xb, ub, x_traj=xt, max_iter=int(max_iter), tol=float(tol),
+                      history=verbose or return_info)
+        finally:
+            if s.h:
+                s.set_tracking(False)  # the mode never outlives the call that asked for it
+            s.close()
     if verbose and r.history is not None:
         from .solver import print_history
         for b in range(xb.shape[0]):

@@ -59,6 +59,11 @@ class MultiSolver:
                  | (_lib.SCHED_REUSE_PER_CALL if reuse_per_call else 0))
         _lib.check(self.lib.ilqr_multi_set_schedule(self.h, flags), "ilqr_multi_set_schedule")
 
+    def set_tracking(self, on: bool = True):
+        """As Solver.set_tracking, on every device's handle (ilqr_multi_set_tracking)."""
+        mode = _lib.TRACK_CONSISTENT if on else _lib.TRACK_FORWARD_ONLY
+        _lib.check(self.lib.ilqr_multi_set_tracking(self.h, mode), "ilqr_multi_set_tracking")
+
     def reuse_record(self, shard: int) -> np.ndarray:
         """Solver.reuse_record of one shard's handle (ilqr_multi_reuse_record)."""
         n = (self.batch + 3) // 4

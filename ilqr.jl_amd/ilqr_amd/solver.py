@@ -145,6 +145,18 @@ class Solver:
                    "ilqr_reuse_record")
         return out[:cnt.value]
 
+    def set_tracking(self, on: bool = True):
+        """Tracking mode of the LQ family (ilqr_set_tracking). Off (a new solver's mode): the
+        reference's behaviour, the backward pass ignores x_traj. On: iterate / fit
+        differentiate the cost the forward pass measures, lx_t = (Q + Qᵀ)(x_t − x_traj_t) for
+        t < T; the end state is still measured raw (include/ilqr.h)."""
+        mode = _lib.TRACK_CONSISTENT if on else _lib.TRACK_FORWARD_ONLY
+        _lib.check(self.lib.ilqr_set_tracking(self.h, mode), "ilqr_set_tracking")
+
+    @property
+    def tracking(self) -> bool:
+        return self.lib.ilqr_get_tracking(self.h) == _lib.TRACK_CONSISTENT
+
     def set_problem(self, lq):
         """lq: LQBatch (host numpy, copied to the device) or a dict of CUDA tensors
         A (B,nx,nx), B (B,nx,nu), Q (B,nx,nx), R (B,nu,nu), Qf (B,nx,nx)."""
@@ -174,19 +186,27 @@ class Solver:
                 f((self.batch, self.T, self.nu), dtype=torch.float64, device=self.dev))
 
     # -- passes ----------------------------------------------------------------------
-    def backward(self, x, u, mu=None):
+    def backward(self, x, u, mu=None, x_traj=None):
         """iLQR.backward_pass for the batch → (d (B,T,nu), K (B,T,nu,nx), status (B,)).
-        Synchronises (folds the per-trajectory NaN status)."""
+        Synchronises (folds the per-trajectory NaN status). x_traj: backward_pass of the
+        tracking cost instead (ilqr_backward_tracking, LQ family, whatever the solver's
+        tracking mode)."""
         B, T, nx, nu = self.batch, self.T, self.nx, self.nu
         _req(x, torch.float64, (B, T + 1, nx), "x")
         _req(u, torch.float64, (B, T, nu), "u")
+        if x_traj is not None:
+            _req(x_traj, torch.float64, (B, T + 1, nx), "x_traj")
         d = torch.empty((B, T, nu), dtype=torch.float64, device=self.dev)
         K = torch.empty((B, T, nu, nx), dtype=torch.float64, device=self.dev)
         st = torch.empty((B,), dtype=torch.int32, device=self.dev)
         self._bind_stream()
         o = _lib.default_options(mu=mu)
-        rc = self.lib.ilqr_backward(self.h, self._p(), C.byref(o), _ptr(x), _ptr(u), _ptr(d),
-                                    _ptr(K), _ptr(st))
+        if x_traj is not None:
+            rc = self.lib.ilqr_backward_tracking(self.h, self._p(), C.byref(o), _ptr(x), _ptr(u), _ptr(x_traj),
+                                                 _ptr(d), _ptr(K), _ptr(st))
+        else:
+            rc = self.lib.ilqr_backward(self.h, self._p(), C.byref(o), _ptr(x), _ptr(u), _ptr(d),
+                                        _ptr(K), _ptr(st))
         _lib.check(rc, "ilqr_backward", allow=(_lib.ERR_NAN,))
         return d, K, st
 

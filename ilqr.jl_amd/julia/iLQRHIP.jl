@@ -187,6 +187,16 @@ const ILQR_SCHED_REUSE_PER_CALL = Int32(256)
 set_schedule!(h::Handle, flags::Integer) =
     check(ccall((:ilqr_set_schedule, libilqr), Cint, (Ptr{Cvoid}, Cint), h.ptr, flags), "ilqr_set_schedule")
 
+# tracking mode of the LQ family (include/ilqr.h: ILQR_TRACK_*): off, the reference's
+# behaviour (backward_pass ignores x_traj); on, the backward differentiates the cost the
+# forward measures, lx_t = (Q + Qᵀ)(x_t − x_traj_t) for t < T (the end state stays raw)
+const ILQR_TRACK_FORWARD_ONLY = Int32(0)
+const ILQR_TRACK_CONSISTENT = Int32(1)
+set_tracking!(h::Handle, on::Bool) =
+    check(ccall((:ilqr_set_tracking, libilqr), Cint, (Ptr{Cvoid}, Int32), h.ptr,
+                on ? ILQR_TRACK_CONSISTENT : ILQR_TRACK_FORWARD_ONLY), "ilqr_set_tracking")
+tracking(h::Handle) = ccall((:ilqr_get_tracking, libilqr), Int32, (Ptr{Cvoid},), h.ptr) == ILQR_TRACK_CONSISTENT
+
 function alloc(h::Handle, T::Type, n)
     p = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:ilqr_malloc, libilqr), Cint, (Ptr{Cvoid}, Csize_t, Ref{Ptr{Cvoid}}), h.ptr, max(n, 1) * sizeof(T), p), "ilqr_malloc")
@@ -360,23 +370,33 @@ function print_history(cost::AbstractVector, trials::AbstractVector)
     end
 end
 
-"""fit(x_init, u_init, dynamicsf, immediate_cost, final_cost; x_traj, max_iter, tol, verbose) -> (x̄, ū)
+"""fit(x_init, u_init, dynamicsf, immediate_cost, final_cost; x_traj, max_iter, tol, verbose, track) -> (x̄, ū)
 
 verbose = true prints the reference's `Iteration: i  Total Cost: c` line for every
-iteration (forward_pass.jl:167), from the device fit's history (ilqr_fit_ex)."""
+iteration (forward_pass.jl:167), from the device fit's history (ilqr_fit_ex).
+track = true (the LQ family only): the backward pass differentiates the tracking cost the
+forward pass measures (set_tracking!); false is the reference's behaviour."""
 function fit(x_init::AbstractMatrix, u_init::AbstractMatrix, dynamicsf, immediate_cost, final_cost;
-             x_traj=zero(x_init), max_iter::Int64=100, tol::Float64=1e-6, verbose::Bool=false)
+             x_traj=zero(x_init), max_iter::Int64=100, tol::Float64=1e-6, verbose::Bool=false,
+             track::Bool=false)
     N, nx = size(x_init); M, nu = size(u_init)
     @assert(N == M + 1, "size(x_init)[2] == size(u_init)[1]")          # forward_pass.jl:156
     fam = family(dynamicsf, immediate_cost, final_cost)
+    track && fam != :lq &&
+        throw(ArgumentError("track = true is implemented for the LQ family only (LinearDynamics, QuadraticCost, QuadraticFinalCost)"))
     fam == :tiles &&
         return fit_tiles(x_init, u_init, dynamicsf, immediate_cost, final_cost, x_traj, max_iter, tol, verbose)
     fam == :floating && return floating_fit1(dynamicsf, x_init, u_init, x_traj, max_iter, tol, verbose)
     # the resident solver of this shape: an MPC loop calling fit allocates nothing per call;
     # an exhausted line search returns the last iterate (fit_resident!)
     return with_cached(SOLVER_CACHE, () -> Solver(nx, nu, M, 1), (nx, nu, M)) do s
-        fit!(set_problem!(s, dynamicsf, immediate_cost, final_cost), x_init, u_init;
-             x_traj=x_traj, max_iter=max_iter, tol=tol, verbose=verbose)
+        set_tracking!(s, track)          # the cached solver's mode never outlives the call
+        try
+            fit!(set_problem!(s, dynamicsf, immediate_cost, final_cost), x_init, u_init;
+                 x_traj=x_traj, max_iter=max_iter, tol=tol, verbose=verbose)
+        finally
+            set_tracking!(s, false)
+        end
     end
 end
 
@@ -487,6 +507,12 @@ function MultiSolver(prob::iLQRProblem, devices::Vector{Int})
     end
     return ms
 end
+
+"""set_tracking!(ms::MultiSolver, on): the tracking mode of every device's handle
+(ilqr_multi_set_tracking); read by the fits that are given an x_traj."""
+set_tracking!(ms::MultiSolver, on::Bool) =
+    check(ccall((:ilqr_multi_set_tracking, libilqr), Cint, (Ptr{Cvoid}, Int32), ms.ptr,
+                on ? ILQR_TRACK_CONSISTENT : ILQR_TRACK_FORWARD_ONLY), "ilqr_multi_set_tracking")
 
 function Base.close(ms::MultiSolver)
     ms.ptr == C_NULL && return
@@ -618,6 +644,11 @@ function ensure_history!(s::Solver, n::Int)
     return Ref(History(s.hc, s.ht, C_NULL, C_NULL))
 end
 
+"""set_tracking!(s::Solver, on): the solver's tracking mode (ilqr_set_tracking): fit! and
+solve! with an x_traj then differentiate the tracking cost. backward!(s, x, u, x_traj) is
+its backward pass whatever the mode."""
+set_tracking!(s::Solver, on::Bool) = set_tracking!(s.h, on)
+
 # ilqr_fit_ex from the resident (x, u, x_traj) into the resident results
 function fit_resident!(s::Solver, max_iter::Int64, tol::Float64, verbose::Bool)
     s.kind == 0 && throw(ArgumentError("set_problem! first"))
@@ -674,6 +705,20 @@ function backward!(s::Solver, x::AbstractMatrix, u::AbstractMatrix)
     check(ccall((:ilqr_backward, libilqr), Cint,
                 (Ptr{Cvoid}, Ref{Problem}, Ref{Options}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
                 s.h.ptr, problem_ref(s), default_options(), s.x, s.u, s.d, s.K, s.status), "ilqr_backward")
+    return from_abi(download!(s.h, zeros(nu, M), s.d)), gains_from_abi(download!(s.h, zeros(nx, nu, M), s.K))
+end
+
+"""backward!(s, x, u, x_traj) -> (δu, K): backward_pass of the tracking cost
+(ilqr_backward_tracking): lx_t = (Q + Qᵀ)(x_t − x_traj_t) for t < T, the LQ family only."""
+function backward!(s::Solver, x::AbstractMatrix, u::AbstractMatrix, x_traj::AbstractMatrix)
+    N, nx = size(x); M, nu = size(u)
+    @assert(N == M + 1)                                                 # backward_pass.jl:329
+    upload!(s.h, s.x, to_abi(x)); upload!(s.h, s.u, to_abi(u)); upload!(s.h, s.xt, to_abi(x_traj))
+    check(ccall((:ilqr_backward_tracking, libilqr), Cint,
+                (Ptr{Cvoid}, Ref{Problem}, Ref{Options}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Int32}),
+                s.h.ptr, problem_ref(s), default_options(), s.x, s.u, s.xt, s.d, s.K, s.status),
+          "ilqr_backward_tracking")
     return from_abi(download!(s.h, zeros(nu, M), s.d)), gains_from_abi(download!(s.h, zeros(nx, nu, M), s.K))
 end
 

@@ -226,6 +226,37 @@ ilqr_status ilqr_set_schedule(ilqr_handle* h, int flags);
  * problem kind, ILQR_SCHED_FULL_BACKWARD). */
 ilqr_status ilqr_reuse_record(ilqr_handle* h, int32_t* out, int32_t capacity, int32_t* count);
 
+/* Tracking mode of the LQ family: which cost ilqr_iterate / ilqr_fit / ilqr_fit_ex
+ * differentiate when they are given an x_traj.
+ *   ILQR_TRACK_FORWARD_ONLY (a new handle's mode) the reference's behaviour, kept literally:
+ *                           total_cost measures l(x_k - x_traj_k, u_k) for k < N and l_f(x_N)
+ *                           on the raw end state (forward_pass.jl:185-193), backward_pass never
+ *                           sees x_traj (:162), so the gains steer toward the origin.
+ *   ILQR_TRACK_CONSISTENT   the backward pass differentiates the cost the forward pass measures:
+ *                           lx_t = (Q + Q')(x_t - x_traj_t) for t < T. lu_t, the Hessians, the
+ *                           dynamics and the regularisation are unchanged, and so are the forward
+ *                           pass, the line search, the convergence test and every status rule. The
+ *                           terminal value function stays S = Qf + Qf', s = S x_N on the raw x_N,
+ *                           as total_cost applies it (:192): row T of x_traj is not read by the
+ *                           backward, and a caller who wants to end on the reference chooses Qf
+ *                           accordingly. x_traj == NULL means zeros: the call then launches what
+ *                           the plain mode launches and returns its bits.
+ * x_traj is vector-side data of the gain reuse (ILQR_SCHED_FULL_BACKWARD above): K_t and the
+ * factor of H + mu I do not depend on it or on the mode, the operand snapshot holds neither, so
+ * a fit whose reference alone changed reuses the stored gains, and switching the mode between
+ * fits KEEPS them (the next fit's check decides by the problem's operands as always).
+ * With ILQR_TRACK_CONSISTENT a call whose p->kind is ILQR_PROBLEM_TWO_LINK returns
+ * ILQR_ERR_UNSUPPORTED before any launch. ilqr_backward and ilqr_forward do not read the mode
+ * (ilqr_backward_tracking below is the backward of the tracking cost). A padded handle
+ * (nx < 12 or nu < 4) forwards the mode to its inner (12, 4) handle.
+ * ilqr_set_tracking: a NULL handle or an unknown mode returns ILQR_ERR_BAD_ARG before any
+ * device call and leaves the mode as it was; it allocates nothing. ilqr_get_tracking: the
+ * mode, -1 for a NULL handle. */
+#define ILQR_TRACK_FORWARD_ONLY 0
+#define ILQR_TRACK_CONSISTENT 1
+ilqr_status ilqr_set_tracking(ilqr_handle* h, int32_t mode);
+int32_t ilqr_get_tracking(const ilqr_handle* h);
+
 /* iLQR.backward_pass (backward_pass.jl:324-357): gains d (batch,T,nu) and
  * K (batch,T,nu,nx) for every trajectory. With a status array (batch) the call
  * synchronises and returns ILQR_ERR_NAN if any trajectory produced a NaN gain;
@@ -233,6 +264,14 @@ ilqr_status ilqr_reuse_record(ilqr_handle* h, int32_t* out, int32_t capacity, in
 ilqr_status ilqr_backward(ilqr_handle* h, const ilqr_problem* p, const ilqr_options* o,
                           const double* x, const double* u, double* d, double* K,
                           int32_t* status);
+
+/* backward_pass of the tracking cost (ILQR_TRACK_CONSISTENT above), LQ family only
+ * (TWO_LINK: ILQR_ERR_UNSUPPORTED): ilqr_backward with lx_t = (Q + Q')(x_t - x_traj_t) for
+ * t < T; x_traj (batch, T+1, nx), row T not read. Whatever the handle's mode. x_traj == NULL
+ * gives ilqr_backward's result, bit for bit. Status and synchronisation as ilqr_backward. */
+ilqr_status ilqr_backward_tracking(ilqr_handle* h, const ilqr_problem* p, const ilqr_options* o,
+                                   const double* x, const double* u, const double* x_traj,
+                                   double* d, double* K, int32_t* status);
 
 /* iLQR.backward_pass for arbitrary closures: the Riccati recursion of
  * backward_pass.jl:335-357 (optimal_controller_param, feedback_parameters,
@@ -557,6 +596,10 @@ ilqr_status ilqr_multi_create(ilqr_multi** out, const int* devices, int n_device
                               int T, int batch);
 ilqr_status ilqr_multi_destroy(ilqr_multi* m);
 ilqr_status ilqr_multi_set_schedule(ilqr_multi* m, int flags);
+/* ilqr_set_tracking on every shard's handle: ilqr_multi_fit, and ilqr_multi_fit_resident with
+ * ILQR_MULTI_USE_X_TRAJ, then differentiate the tracking cost. A NULL m or an unknown mode
+ * returns ILQR_ERR_BAD_ARG and changes no shard. */
+ilqr_status ilqr_multi_set_tracking(ilqr_multi* m, int32_t mode);
 int ilqr_multi_devices(const ilqr_multi* m);
 /* ilqr_reuse_record of shard `shard`'s handle (0 .. ilqr_multi_devices - 1; its waves count
  * from the shard's first trajectory). */
