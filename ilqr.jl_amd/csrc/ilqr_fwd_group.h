@@ -293,7 +293,7 @@ inline hipError_t fg_with_lanes(int B, bool wide, Fn&& fn) {
 // ---------------------------------------------------------------------------
 // The results of a forward, written once its line search has ended: fwd_iter_finish by
 // every fit-iteration forward kernel of the 2-link and chain families (whatever rolled the
-// trajectory out), fwd_finish by the six-joint standalone forward
+// trajectory out), fwd_finish by the tiles path's standalone forward (ilqr_chain_tiles.hip)
 // ---------------------------------------------------------------------------
 
 // A standalone forward (ilqr_chain_forward) of trajectory b, called by every lane of its

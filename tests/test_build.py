@@ -43,6 +43,7 @@ def test_restore_alternates_patch_builds(tmp_path):
     csrc = tmp_path / "ilqr.jl_amd" / "csrc"
     base = [_hipcc(), "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-c"]
     mf = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
+    chain = mf + ["-fno-slp-vectorize", "-DILQR_CHAIN_FD_ROT=0", "-DILQR_CHAIN_FD_PAIR=0", "-DILQR_CHAIN_F2_FAST=0"]
     jobs = [
         # the backward with the round-2 instruction cuts undone, slot loads without nt; the
         # cooperative search in four-trial grabs, its hand-out key without the deep class and
@@ -54,14 +55,14 @@ def test_restore_alternates_patch_builds(tmp_path):
         ["-DILQR_FW_LDS_BCAST=1", "-DILQR_FW_WAVES=1", "-DILQR_FW_ABLATE=3", "ilqr_lq.hip"],
         # the 2-link forward on the generic RK4 with a 4-deep prefetch
         mf + ["-DILQR_TL_RK4_SHIFT=0", "-DILQR_FW_GROUP_PF=4", "ilqr_twolink.hip"],
-        # the chain's Rodrigues-form central differences, unpacked ±h and fp32 step
-        mf + ["-fno-slp-vectorize", "-DILQR_CHAIN_FD_ROT=0", "-DILQR_CHAIN_FD_PAIR=0",
-              "-DILQR_CHAIN_F2_FAST=0", "ilqr_chain.hip"],
+        # the chain's Rodrigues-form central differences, unpacked ±h and fp32 step: the 2-joint
+        # object and the tiles path's object of every joint count (below)
+        chain + ["ilqr_chain.hip"],
         # the fused kernel's de-phase probe, the sixteen-trial pass with one exchange a step
         mf + ["-DILQR_FUSED_DEPHASE_PROBE=1", "-DILQR_CAND16_FORM=2", "ilqr_bw4.hip"],
         # the floating forward's two-barrier rollout on three waves
         ["-ffp-contract=on", "-DILQR_FB_LOOKAHEAD=0", "ilqr_floating.hip"],
-    ]
+    ] + [chain + [f"-DILQR_CHAIN_NJ={nj}", "ilqr_chain_tiles.hip"] for nj in (4, 5, 6, 7)]
 
     def build(job):
         i, args = job
@@ -69,6 +70,6 @@ def test_restore_alternates_patch_builds(tmp_path):
         cmd = base + args[:-1] + [str(csrc / src), "-o", str(tmp_path / f"{src}.{i}.o")]
         return src, subprocess.run(cmd, capture_output=True, text=True, timeout=900)
 
-    with ThreadPoolExecutor(4) as ex:
+    with ThreadPoolExecutor(8) as ex:
         for src, r in ex.map(build, enumerate(jobs)):
             assert r.returncode == 0, (src, r.stderr[-2000:])
