@@ -23,6 +23,10 @@ struct ilqr_handle {
   int device = 0;
   int nx = 0, nu = 0, T = 0, batch = 0;
   hipStream_t stream = nullptr;
+  // everything below that lives on the device, in pinned memory or in the runtime is acquired
+  // through `own` in ilqr_create and released with the handle; `pad_own` is the padded
+  // scratch's group (ensure_pad)
+  ilqr::HipOwned own, pad_own;
   // workspace (fit): ping-pong trajectories, gains, per-trajectory state
   double* xbuf[2] = {nullptr, nullptr};
   double* ubuf[2] = {nullptr, nullptr};
@@ -141,16 +145,7 @@ namespace {
 
 thread_local std::string g_last_error;
 
-ilqr_status hip_fail(hipError_t e, const char* what) {
-  g_last_error = std::string(what) + ": " + hipGetErrorString(e);
-  return ILQR_ERR_HIP;
-}
-
-#define HIP_TRY(expr)                                  \
-  do {                                                 \
-    hipError_t e_ = (expr);                            \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr);  \
-  } while (0)
+#define HIP_TRY(expr) ILQR_HIP_TRY(g_last_error, expr)
 
 ilqr::LQParams lq_params(const ilqr_problem* p) {
   return ilqr::LQParams{p->A, p->B, p->Q, p->R, p->Qf};
@@ -263,28 +258,34 @@ ilqr_status join(ilqr_handle* h, const ilqr_problem* p) {
 
 // Inner (12, 4) handle and padded scratch, created on the first padded call (the
 // only allocation outside ilqr_create); stream and schedule follow the outer handle.
+// h->pad is published only once the whole group exists: a failure releases what was made,
+// and the next padded call starts again from nothing.
 ilqr_status ensure_pad(ilqr_handle* h) {
   if (!h->pad) {
     ilqr_handle* in = nullptr;
     const ilqr_status st = ilqr_create(&in, h->device, PAD_NX, PAD_NU, h->T, h->batch);
     if (st != ILQR_OK) return st;
-    h->pad = in;
     const size_t B = (size_t)h->batch, T = (size_t)h->T;
-    hipError_t e = hipSuccess;
-    auto al = [&](double** q, size_t n) { if (e == hipSuccess) e = hipMalloc(q, sizeof(double) * n); };
-    al(&h->pA, B * PAD_NX * PAD_NX);
-    al(&h->pB, B * PAD_NX * PAD_NU);
-    al(&h->pQ, B * PAD_NX * PAD_NX);
-    al(&h->pR, B * PAD_NU * PAD_NU);
-    al(&h->pQf, B * PAD_NX * PAD_NX);
-    al(&h->px, B * (T + 1) * PAD_NX);
-    al(&h->pxt, B * (T + 1) * PAD_NX);
-    al(&h->pxn, B * (T + 1) * PAD_NX);
-    al(&h->pu, B * T * PAD_NU);
-    al(&h->pun, B * T * PAD_NU);
-    al(&h->pd, B * T * PAD_NU);
-    al(&h->pK, B * T * PAD_NU * PAD_NX);
-    if (e != hipSuccess) return hip_fail(e, "ilqr: padded workspace");
+    ilqr::HipOwned& own = h->pad_own;
+    own.dev(&h->pA, B * PAD_NX * PAD_NX);
+    own.dev(&h->pB, B * PAD_NX * PAD_NU);
+    own.dev(&h->pQ, B * PAD_NX * PAD_NX);
+    own.dev(&h->pR, B * PAD_NU * PAD_NU);
+    own.dev(&h->pQf, B * PAD_NX * PAD_NX);
+    own.dev(&h->px, B * (T + 1) * PAD_NX);
+    own.dev(&h->pxt, B * (T + 1) * PAD_NX);
+    own.dev(&h->pxn, B * (T + 1) * PAD_NX);
+    own.dev(&h->pu, B * T * PAD_NU);
+    own.dev(&h->pun, B * T * PAD_NU);
+    own.dev(&h->pd, B * T * PAD_NU);
+    own.dev(&h->pK, B * T * PAD_NU * PAD_NX);
+    if (!own.ok()) {
+      const hipError_t e = own.error();
+      own.release();
+      (void)ilqr_destroy(in);
+      return ilqr::hip_fail(g_last_error, e, "ilqr: padded workspace");
+    }
+    h->pad = in;
   }
   h->pad->stream = h->stream;
   h->pad->pipelined = h->pipelined;
@@ -431,71 +432,58 @@ ilqr_status ilqr_create(ilqr_handle** out, int device, int nx, int nu, int T, in
   h->batch = batch;
   h->bw_wave = batch < BW4_MIN_BATCH;
   const size_t B = (size_t)batch;
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-    e = hipMalloc(&h->xbuf[i], sizeof(double) * B * (T + 1) * nx);
-    if (e == hipSuccess) e = hipMalloc(&h->ubuf[i], sizeof(double) * B * T * nu);
+  ilqr::HipOwned& own = h->own;
+  own.set_device(device);
+  h->pad_own.set_device(device);
+  for (int i = 0; i < 2; ++i) {
+    own.dev(&h->xbuf[i], B * (T + 1) * nx);
+    own.dev(&h->ubuf[i], B * T * nu);
   }
-  if (e == hipSuccess) e = hipMalloc(&h->K, sizeof(double) * B * T * nu * nx);
-  if (e == hipSuccess) e = hipMalloc(&h->d, sizeof(double) * B * T * nu);
-  if (e == hipSuccess) e = ilqr::fit_state_create(&h->fit, B, sizeof(double));
-  if (e == hipSuccess) e = hipHostMalloc(&h->host_status, sizeof(int32_t) * B, hipHostMallocDefault);
-  if (e == hipSuccess && nx == 12 && nu == 4) {
-    e = hipMalloc(&h->coop_rec, sizeof(ilqr::LSCoopRec) * B);
-    if (e == hipSuccess) e = hipMalloc(&h->coop_cost, sizeof(double) * B * ilqr::COOP_MAX_TRIALS);
-    if (e == hipSuccess) e = hipMalloc(&h->coop_du2, sizeof(double) * B * ilqr::COOP_MAX_TRIALS);
-    if (e == hipSuccess) e = hipMalloc(&h->coop_list, sizeof(uint64_t) * B);
-    if (e == hipSuccess) e = hipMalloc(&h->coop_ctl, sizeof(int32_t) * 2);
-    if (e == hipSuccess) e = hipMemset(h->coop_list, 0, sizeof(uint64_t) * B);  // generation 0: stale
-    if (e == hipSuccess) e = hipMemset(h->coop_ctl, 0, sizeof(int32_t) * 2);
-    if (e == hipSuccess) e = hipMalloc(&h->coop_dev, sizeof(ilqr::LSCoop));
+  own.dev(&h->K, B * T * nu * nx);
+  own.dev(&h->d, B * T * nu);
+  hipError_t e = ilqr::fit_state_create(&h->fit, own, B, sizeof(double));
+  own.pinned(&h->host_status, B, hipHostMallocDefault);
+  int nsl = 0;  // the search's scratch slots
+  if (nx == 12 && nu == 4) {
+    own.dev(&h->coop_rec, B);
+    own.dev(&h->coop_cost, B * ilqr::COOP_MAX_TRIALS);
+    own.dev(&h->coop_du2, B * ilqr::COOP_MAX_TRIALS);
+    own.dev_zero(&h->coop_list, B);  // generation 0: stale
+    own.dev_zero(&h->coop_ctl, 2);
+    own.dev(&h->coop_dev, 1);
     // scratch rollouts for the first searches of a launch (32-bit buffer offsets: the
     // x part must stay under 2 GiB, else no scratch)
-    const int nsl = std::min(batch, ilqr::COOP_SCRATCH_SLOTS);
-    const size_t sxb = sizeof(double) * nsl * ilqr::COOP_MAX_TRIALS * (size_t)(T + 1) * nx;
-    const size_t sub = sizeof(double) * nsl * ilqr::COOP_MAX_TRIALS * (size_t)T * nu;
-    bool scratch = sxb < (size_t(1) << 31);
+    nsl = std::min(batch, ilqr::COOP_SCRATCH_SLOTS);
+    const size_t sx = (size_t)nsl * ilqr::COOP_MAX_TRIALS * (size_t)(T + 1) * nx;
+    const size_t su = (size_t)nsl * ilqr::COOP_MAX_TRIALS * (size_t)T * nu;
     // the scratch (≈260 MB at T = 1000) is a speed-up, not a need: without it the search
     // rolls the final trial out again (nslots = 0), so a failed allocation is not an error
-    if (e == hipSuccess && scratch && hipMalloc(&h->coop_sx, sxb) != hipSuccess) scratch = false;
-    if (e == hipSuccess && scratch && hipMalloc(&h->coop_su, sub) != hipSuccess) scratch = false;
-    if (!scratch) {
-      (void)hipGetLastError();  // clear the failed allocation's error
-      (void)hipFree(h->coop_sx);
-      (void)hipFree(h->coop_su);
-      h->coop_sx = nullptr;
-      h->coop_su = nullptr;
-    }
-    if (e == hipSuccess) {
-      const ilqr::LSCoop c{h->coop_rec, h->coop_cost, h->coop_du2, h->coop_list, h->coop_ctl,
-                           h->coop_sx,  h->coop_su,   scratch ? nsl : 0};
-      e = hipMemcpy(h->coop_dev, &c, sizeof(c), hipMemcpyHostToDevice);
+    const bool fits = sizeof(double) * sx < (size_t(1) << 31);
+    if (!(fits && own.try_dev(&h->coop_sx, sx) && own.try_dev(&h->coop_su, su))) {
+      own.drop(&h->coop_sx);
+      nsl = 0;
     }
     // the backward's factor of H + μI of one fit's first iteration (80 B per trajectory
-    // and step, 33 MB at B = 4096, T = 100); like the scratch a speed-up, not a need
-    if (e == hipSuccess && hipMalloc(&h->fac, sizeof(double) * ilqr::lq_fac_doubles(B, T)) != hipSuccess) {
-      (void)hipGetLastError();
-      h->fac = nullptr;
-    }
-    // the operand snapshot of those gains (31 doubles per lane: the size of the problem
+    // and step, 33 MB at B = 4096, T = 100); like the scratch a speed-up, not a need.
+    // The operand snapshot of those gains (31 doubles per lane: the size of the problem
     // itself, 16 MB at B = 4096) and the per-wave branch record; without them reuse stays
     // within one call
-    if (e == hipSuccess && h->fac &&
-        (hipMalloc(&h->snap, sizeof(double) * ilqr::lq_snap_doubles(B)) != hipSuccess ||
-         hipMalloc(&h->branch, sizeof(int32_t) * ilqr::lq_fused_waves(B)) != hipSuccess)) {
-      (void)hipGetLastError();
-      (void)hipFree(h->snap);
-      h->snap = nullptr;
-      h->branch = nullptr;
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (own.try_dev(&h->fac, ilqr::lq_fac_doubles(B, T)) &&
+        !(own.try_dev(&h->snap, ilqr::lq_snap_doubles(B)) && own.try_dev(&h->branch, ilqr::lq_fused_waves(B))))
+      own.drop(&h->snap);
   }
-  if (e == hipSuccess && ilqr::tl_supported(nx, nu))
-    e = hipMalloc(&h->J, sizeof(double) * ilqr::tl_workspace_doubles(batch, T));
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking);
-  for (int c = 0; c < 2 && e == hipSuccess; ++c) {
-    e = hipEventCreateWithFlags(&h->ev_bw[c], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_fw[c], hipEventDisableTiming);
+  if (ilqr::tl_supported(nx, nu)) own.dev(&h->J, ilqr::tl_workspace_doubles(batch, T));
+  own.stream(&h->side, hipStreamNonBlocking);
+  for (int c = 0; c < 2; ++c) {
+    own.event(&h->ev_bw[c], hipEventDisableTiming);
+    own.event(&h->ev_fw[c], hipEventDisableTiming);
+  }
+  if (!own.ok()) e = own.error();
+  if (e == hipSuccess && h->coop_dev) {  // the struct of the search's buffers, and the zeroing done
+    const ilqr::LSCoop c{h->coop_rec, h->coop_cost, h->coop_du2, h->coop_list, h->coop_ctl,
+                         h->coop_sx,  h->coop_su,   nsl};
+    e = hipMemcpy(h->coop_dev, &c, sizeof(c), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
   }
   if (e == hipSuccess) {
     // Two chunks (chunk c's forward on the side stream overlapping chunk c+1's
@@ -512,7 +500,7 @@ ilqr_status ilqr_create(ilqr_handle** out, int device, int nx, int nu, int T, in
   }
   if (e != hipSuccess) {
     ilqr_destroy(h);
-    return hip_fail(e, "ilqr_create: hipMalloc");
+    return ilqr::hip_fail(g_last_error, e, "ilqr_create: hipMalloc");
   }
   *out = h;
   return ILQR_OK;
@@ -520,38 +508,8 @@ ilqr_status ilqr_create(ilqr_handle** out, int device, int nx, int nu, int T, in
 
 ilqr_status ilqr_destroy(ilqr_handle* h) {
   if (!h) return ILQR_OK;
-  (void)hipSetDevice(h->device);
-  for (int i = 0; i < 2; ++i) {
-    (void)hipFree(h->xbuf[i]);
-    (void)hipFree(h->ubuf[i]);
-  }
-  (void)hipFree(h->K);
-  (void)hipFree(h->d);
-  ilqr::fit_state_destroy(&h->fit);
-  if (h->host_status) (void)hipHostFree(h->host_status);
-  (void)hipFree(h->coop_rec);
-  (void)hipFree(h->coop_cost);
-  (void)hipFree(h->coop_du2);
-  (void)hipFree(h->coop_list);
-  (void)hipFree(h->coop_sx);
-  (void)hipFree(h->coop_su);
-  (void)hipFree(h->coop_ctl);
-  (void)hipFree(h->coop_dev);
-  (void)hipFree(h->fac);
-  (void)hipFree(h->snap);
-  (void)hipFree(h->branch);
-  if (h->pad) {
-    (void)ilqr_destroy(h->pad);
-    for (double* q : {h->pA, h->pB, h->pQ, h->pR, h->pQf, h->px, h->pu, h->pxt, h->pxn, h->pun, h->pd, h->pK})
-      (void)hipFree(q);
-  }
-  (void)hipFree(h->J);
-  for (int c = 0; c < 2; ++c) {
-    if (h->ev_bw[c]) (void)hipEventDestroy(h->ev_bw[c]);
-    if (h->ev_fw[c]) (void)hipEventDestroy(h->ev_fw[c]);
-  }
-  if (h->side) (void)hipStreamDestroy(h->side);
-  delete h;
+  (void)ilqr_destroy(h->pad);
+  delete h;  // its owners release
   return ILQR_OK;
 }
 

@@ -1005,16 +1005,14 @@ namespace {
 
 thread_local std::string g_chain_error;
 
-ilqr_status chain_hip_fail(hipError_t e, const char* what) {
-  g_chain_error = std::string(what) + ": " + hipGetErrorString(e);
-  return ILQR_ERR_HIP;
-}
+#define CH_TRY(expr) ILQR_HIP_TRY(g_chain_error, expr)
 
-#define CH_TRY(expr)                                         \
-  do {                                                       \
-    hipError_t e_ = (expr);                                  \
-    if (e_ != hipSuccess) return chain_hip_fail(e_, #expr);  \
-  } while (0)
+// a buffer the handle acquires at its first use and keeps (through its owner, which a failed
+// request must not poison for the next call: an optional request, reported here)
+template <class T>
+hipError_t chain_lazy_dev(ilqr_chain_handle* h, T** p, size_t count) {
+  return *p || h->own.try_dev(p, count) ? hipSuccess : hipErrorOutOfMemory;
+}
 
 // ChainTrig<V> from the fp64 coefficients and the chain's cost
 template <class V>
@@ -1057,7 +1055,10 @@ hipError_t chain_trig_build(ilqr_chain_handle* h) {
   const auto P = chain_consts<double, 2>(h->chain);
   constexpr int NCHK = 256;
   double* dev = nullptr;
-  hipError_t e = hipMalloc(&dev, sizeof(double) * (ilqr::CH_TRIG_SAMPLES + NCHK));
+  ilqr::HipOwned tmp;  // the sample buffer, released on every exit
+  tmp.set_device(h->device);
+  tmp.dev(&dev, ilqr::CH_TRIG_SAMPLES + NCHK);
+  hipError_t e = tmp.error();
   if (e != hipSuccess) return e;
   double smp[ilqr::CH_TRIG_SAMPLES], err[NCHK];
   ilqr::chain_trig_sample_kernel<<<1, 64>>>(P, dev);
@@ -1099,7 +1100,6 @@ hipError_t chain_trig_build(ilqr_chain_handle* h) {
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(err, dev + ilqr::CH_TRIG_SAMPLES, sizeof(err), hipMemcpyDeviceToHost);
-  (void)hipFree(dev);
   if (e != hipSuccess) return e;
   double m = 0.0;
   for (double v : err) m = std::isnan(v) ? INFINITY : std::max(m, v);
@@ -1426,7 +1426,7 @@ ilqr_status chain_set_goal_rows(ilqr_chain_handle* h, const double* targets, siz
   }
   const size_t bytes = sizeof(double) * (size_t)h->batch * width;
   CH_TRY(hipSetDevice(h->device));
-  if (!*rows) CH_TRY(hipMalloc(rows, bytes));
+  CH_TRY(chain_lazy_dev(h, rows, (size_t)h->batch * width));
   CH_TRY(hipMemcpyAsync(*rows, targets, bytes, hipMemcpyDeviceToDevice, h->stream));
   CH_TRY(hipStreamSynchronize(h->stream));
   *on = true;
@@ -1482,49 +1482,47 @@ ilqr_status ilqr_chain_create(ilqr_chain_handle** out, int device, const ilqr_ch
   h->chain = *chain;
   h->created = *chain;
   const size_t w = vsize(h), B = (size_t)batch, nx = 2 * (size_t)h->nj, nu = (size_t)h->nu;
-  hipError_t e = hipSuccess;
   const bool tiles = on_tiles(h);
+  ilqr::HipOwned& own = h->own;
+  own.set_device(device);
+  hipError_t e = hipSuccess;
   if (handle_iterates(h)) {  // dynamics-only shapes need no workspace
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-      e = hipMalloc(&h->xbuf[i], w * B * (T + 1) * nx);
-      if (e == hipSuccess) e = hipMalloc(&h->ubuf[i], w * B * T * nu);
+    for (int i = 0; i < 2; ++i) {
+      own.dev(&h->xbuf[i], w * B * (T + 1) * nx);
+      own.dev(&h->ubuf[i], w * B * T * nu);
     }
-    if (e == hipSuccess) e = hipMalloc(&h->K, w * B * T * nu * nx);
-    if (e == hipSuccess) e = hipMalloc(&h->d, w * B * T * nu);
-    if (e == hipSuccess && !tiles) e = hipMalloc(&h->two.J, w * B * T * (nx * (nx + nu) + nx + nu));
+    own.dev(&h->K, w * B * T * nu * nx);
+    own.dev(&h->d, w * B * T * nu);
+    if (!tiles) own.dev(&h->two.J, w * B * T * (nx * (nx + nu) + nx + nu));
     if (tiles) {  // the tiles in place of the records
       ilqr_chain_handle::Tiles& t = h->tiles;
       // zeroed: stopped trajectories run the recursion on whatever their tiles hold
-      auto tile = [&](double** p, size_t n) {
-        if (e == hipSuccess) e = hipMalloc(p, sizeof(double) * n);
-        if (e == hipSuccess) e = hipMemset(*p, 0, sizeof(double) * n);
-      };
-      tile(&t.tA, B * T * nx * nx);
-      tile(&t.tB, B * T * nx * nu);
-      tile(&t.lx, B * T * nx);
-      tile(&t.lu, B * T * nu);
-      tile(&t.lxx, B * T * nx * nx);
-      tile(&t.luu, B * T * nu * nu);
-      tile(&t.lfx, B * nx);
-      tile(&t.lfxx, B * nx * nx);
-      if (e == hipSuccess) e = hipMalloc(&t.bstatus, sizeof(int32_t) * B);
+      own.dev_zero(&t.tA, B * T * nx * nx);
+      own.dev_zero(&t.tB, B * T * nx * nu);
+      own.dev_zero(&t.lx, B * T * nx);
+      own.dev_zero(&t.lu, B * T * nu);
+      own.dev_zero(&t.lxx, B * T * nx * nx);
+      own.dev_zero(&t.luu, B * T * nu * nu);
+      own.dev_zero(&t.lfx, B * nx);
+      own.dev_zero(&t.lfxx, B * nx * nx);
+      own.dev(&t.bstatus, B);
     }
-    if (e == hipSuccess) e = ilqr::fit_state_create(&h->fit, B, w);
+    e = ilqr::fit_state_create(&h->fit, own, B, w);
   }
   if (e != hipSuccess) {
-    ilqr_chain_destroy(h);
-    return chain_hip_fail(e, "ilqr_chain_create: hipMalloc");
+    delete h;
+    return ilqr::hip_fail(g_chain_error, e, "ilqr_chain_create: hipMalloc");
   }
   if (iter_supported(h->nj, h->nu) && (e = chain_trig_build(h)) != hipSuccess) {
-    ilqr_chain_destroy(h);
-    return chain_hip_fail(e, "ilqr_chain_create: closed-form dynamics");
+    delete h;
+    return ilqr::hip_fail(g_chain_error, e, "ilqr_chain_create: closed-form dynamics");
   }
   if (tiles) {
     e = tiles_table(h)->hessians(h);  // lxx, luu, lfxx of the cost in effect
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) {
-      ilqr_chain_destroy(h);
-      return chain_hip_fail(e, "ilqr_chain_create: cost tiles");
+      delete h;
+      return ilqr::hip_fail(g_chain_error, e, "ilqr_chain_create: cost tiles");
     }
   }
   *out = h;
@@ -1572,7 +1570,7 @@ ilqr_status ilqr_chain_set_simple_costs(ilqr_chain_handle* h, int32_t mode, int3
   }
   CH_TRY(hipSetDevice(h->device));
   CH_TRY(hipStreamSynchronize(h->stream));
-  if (!h->two.task_dev) CH_TRY(hipMalloc(&h->two.task_dev, sizeof(ilqr::ChainTask)));
+  CH_TRY(chain_lazy_dev(h, &h->two.task_dev, 1));
   CH_TRY(hipMemcpy(h->two.task_dev, &C, sizeof(C), hipMemcpyHostToDevice));
   apply_cost_mode(h, mode);
   return ILQR_OK;
@@ -1638,21 +1636,7 @@ int32_t ilqr_chain_get_dynamics(const ilqr_chain_handle* h) {
 double ilqr_chain_closed_form_error(const ilqr_chain_handle* h) { return h ? h->two.trig_err : -1.0; }
 
 ilqr_status ilqr_chain_destroy(ilqr_chain_handle* h) {
-  if (!h) return ILQR_OK;
-  (void)hipSetDevice(h->device);
-  for (int i = 0; i < 2; ++i) {
-    (void)hipFree(h->xbuf[i]);
-    (void)hipFree(h->ubuf[i]);
-  }
-  (void)hipFree(h->K);
-  (void)hipFree(h->d);
-  ilqr::fit_state_destroy(&h->fit);
-  for (void* p : {h->two.J, (void*)h->two.task_dev}) (void)hipFree(p);
-  const ilqr_chain_handle::Tiles& t = h->tiles;
-  for (void* p : {(void*)t.tA, (void*)t.tB, (void*)t.lx, (void*)t.lu, (void*)t.lxx, (void*)t.luu, (void*)t.lfx,
-                  (void*)t.lfxx, (void*)t.bstatus, (void*)t.joint_rows, (void*)t.task_rows})
-    (void)hipFree(p);
-  delete h;
+  delete h;  // its owner releases
   return ILQR_OK;
 }
 

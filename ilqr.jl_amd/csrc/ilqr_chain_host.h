@@ -14,6 +14,9 @@ struct ilqr_chain_handle {
   int lin = ILQR_LINEARIZE_DUAL;
   ilqr_chain chain{};
   hipStream_t stream = nullptr;
+  // every device buffer, pinned word and event below is acquired through `own`: in
+  // ilqr_chain_create, or at its first use (two.task_dev, tiles.joint_rows, tiles.task_rows)
+  ilqr::HipOwned own;
   void* xbuf[2] = {nullptr, nullptr};
   void* ubuf[2] = {nullptr, nullptr};
   void* K = nullptr;

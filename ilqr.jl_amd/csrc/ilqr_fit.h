@@ -36,29 +36,17 @@ struct FitState {
   uint32_t fit_seq = 0;   // fits so far (tags the host call-status word)
 };
 
-// `elem`: bytes of one cost value (4 or 8). On failure the caller destroys what was made.
-inline hipError_t fit_state_create(FitState* f, size_t B, size_t elem) {
-  hipError_t e = hipMalloc(&f->prev_cost, elem * B);
-  if (e == hipSuccess) e = hipMalloc(&f->du2, elem * B);
-  for (int32_t** p : {&f->trials, &f->status, &f->res_parity, &f->iters})
-    if (e == hipSuccess) e = hipMalloc(p, sizeof(int32_t) * B);
-  if (e == hipSuccess)
-    e = hipHostMalloc(&f->host_words, sizeof(int32_t) * 4, hipHostMallocMapped | hipHostMallocCoherent);
-  if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&f->dev_words, f->host_words, 0);
-  if (e == hipSuccess) e = hipMalloc(&f->dev_flags, sizeof(int32_t) * 2);
-  if (e == hipSuccess) e = hipMemset(f->dev_flags, 0, sizeof(int32_t) * 2);
-  for (int c = 0; c < 2 && e == hipSuccess; ++c) e = hipEventCreateWithFlags(&f->ev_poll[c], hipEventDisableTiming);
-  return e;
-}
-
-inline void fit_state_destroy(FitState* f) {
-  for (void* p : {f->prev_cost, f->du2, (void*)f->trials, (void*)f->status, (void*)f->res_parity, (void*)f->iters,
-                  (void*)f->dev_flags})
-    (void)hipFree(p);
-  if (f->host_words) (void)hipHostFree(f->host_words);
-  for (hipEvent_t ev : f->ev_poll)
-    if (ev) (void)hipEventDestroy(ev);
-  *f = FitState{};
+// `elem`: bytes of one cost value (4 or 8). Everything is acquired through the handle's owner
+// (which releases it); the owner's first error, or the device alias's, is returned.
+inline hipError_t fit_state_create(FitState* f, HipOwned& own, size_t B, size_t elem) {
+  own.dev(&f->prev_cost, elem * B);
+  own.dev(&f->du2, elem * B);
+  for (int32_t** p : {&f->trials, &f->status, &f->res_parity, &f->iters}) own.dev(p, B);
+  own.pinned(&f->host_words, 4, hipHostMallocMapped | hipHostMallocCoherent);
+  own.dev_zero(&f->dev_flags, 2);
+  for (hipEvent_t& ev : f->ev_poll) own.event(&ev, hipEventDisableTiming);
+  if (!own.ok()) return own.error();
+  return hipHostGetDevicePointer((void**)&f->dev_words, f->host_words, 0);
 }
 
 // One fit call. The caller fills the first block; fit_begin sets the second.

@@ -1545,6 +1545,7 @@ struct ilqr_floating_handle {
   ilqr::FbModel model{};
   ilqr::FbModel* model_dev = nullptr;
   hipStream_t stream = nullptr;
+  ilqr::HipOwned own;  // acquires everything below in ilqr_floating_create, releases it with the handle
   double *xbuf[2] = {nullptr, nullptr}, *ubuf[2] = {nullptr, nullptr};  // fit's ping-pong iterates
   double *d = nullptr, *K = nullptr;
   double *A = nullptr, *Bm = nullptr, *lx = nullptr, *lu = nullptr, *lxx = nullptr, *luu = nullptr;
@@ -1561,16 +1562,7 @@ namespace {
 
 thread_local std::string g_fb_error;
 
-ilqr_status fb_fail(hipError_t e, const char* what) {
-  g_fb_error = std::string(what) + ": " + hipGetErrorString(e);
-  return ILQR_ERR_HIP;
-}
-
-#define FB_TRY(expr)                                    \
-  do {                                                  \
-    hipError_t e_ = (expr);                             \
-    if (e_ != hipSuccess) return fb_fail(e_, #expr);    \
-  } while (0)
+#define FB_TRY(expr) ILQR_HIP_TRY(g_fb_error, expr)
 
 // the model from the ABI description (fp64 products formed on the host)
 bool fb_model(const ilqr_floating* m, ilqr::FbModel& P) {
@@ -1727,51 +1719,42 @@ ilqr_status ilqr_floating_create(ilqr_floating_handle** out, int device, const i
   h->T = T;
   h->batch = batch;
   const size_t B = (size_t)batch, nx = ilqr::FB_NX, nu = ilqr::FB_NU, P = B * T;
-  hipError_t e = hipSuccess;
-  auto alloc = [&](auto** p, size_t bytes) {
-    if (e == hipSuccess) e = hipMalloc((void**)p, bytes);
-  };
+  ilqr::HipOwned& own = h->own;
+  own.set_device(device);
   for (int i = 0; i < 2; ++i) {
-    alloc(&h->xbuf[i], 8 * B * (T + 1) * nx);
-    alloc(&h->ubuf[i], 8 * P * nu);
+    own.dev(&h->xbuf[i], B * (T + 1) * nx);
+    own.dev(&h->ubuf[i], P * nu);
   }
-  alloc(&h->d, 8 * P * nu);
-  alloc(&h->K, 8 * P * nu * nx);
-  alloc(&h->A, 8 * P * nx * nx);
-  alloc(&h->Bm, 8 * P * nx * nu);
-  alloc(&h->lx, 8 * P * nx);
-  alloc(&h->lu, 8 * P * nu);
-  alloc(&h->lxx, 8 * P * nx * nx);
-  alloc(&h->luu, 8 * P * nu * nu);
-  alloc(&h->lfx, 8 * B * nx);
-  alloc(&h->lfxx, 8 * B * nx * nx);
-  alloc(&h->cost, 8 * B);
-  alloc(&h->fstatus, 4 * B);
-  alloc(&h->bstatus, 4 * B);
-  alloc(&h->move, 4 * B);
-  if (e == hipSuccess) e = ilqr::fit_state_create(&h->fit, B, 8);
+  own.dev(&h->d, P * nu);
+  own.dev(&h->K, P * nu * nx);
+  own.dev(&h->A, P * nx * nx);
+  own.dev(&h->Bm, P * nx * nu);
+  own.dev(&h->lx, P * nx);
+  own.dev(&h->lu, P * nu);
+  own.dev(&h->lxx, P * nx * nx);
+  own.dev(&h->luu, P * nu * nu);
+  own.dev(&h->lfx, B * nx);
+  own.dev(&h->lfxx, B * nx * nx);
+  own.dev(&h->cost, B);
+  own.dev(&h->fstatus, B);
+  own.dev(&h->bstatus, B);
+  own.dev(&h->move, B);
+  hipError_t e = ilqr::fit_state_create(&h->fit, own, B, 8);
   h->cand = fb_cand(batch, T);
-  alloc(&h->slots, 8 * fb_slot_doubles(batch, T, h->cand));
-  alloc(&h->model_dev, sizeof(ilqr::FbModel));
+  own.dev(&h->slots, fb_slot_doubles(batch, T, h->cand));
+  own.dev(&h->model_dev, 1);
+  if (!own.ok()) e = own.error();
   if (e == hipSuccess) e = hipMemcpy(h->model_dev, &h->model, sizeof(ilqr::FbModel), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
-    ilqr_floating_destroy(h);
-    return fb_fail(e, "ilqr_floating_create: hipMalloc");
+    delete h;
+    return ilqr::hip_fail(g_fb_error, e, "ilqr_floating_create: hipMalloc");
   }
   *out = h;
   return ILQR_OK;
 }
 
 ilqr_status ilqr_floating_destroy(ilqr_floating_handle* h) {
-  if (!h) return ILQR_OK;
-  (void)hipSetDevice(h->device);
-  for (double* p : {h->xbuf[0], h->ubuf[0], h->xbuf[1], h->ubuf[1], h->d, h->K, h->A, h->Bm, h->lx, h->lu, h->lxx,
-                    h->luu, h->lfx, h->lfxx, h->cost, h->slots})
-    (void)hipFree(p);
-  for (int32_t* p : {h->fstatus, h->bstatus, h->move}) (void)hipFree(p);
-  ilqr::fit_state_destroy(&h->fit);
-  (void)hipFree(h->model_dev);
-  delete h;
+  delete h;  // its owner releases
   return ILQR_OK;
 }
 

@@ -5,10 +5,47 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <string>
+
 #include "../../include/ilqr.h"
+#include "ilqr_owned.h"
 #include "ilqr_wait.h"
 
 namespace ilqr {
+
+// The HIP runtime behind every handle's owner (ilqr_owned.h): the only place of the library
+// that acquires or releases device memory, pinned memory, events and streams, beside the
+// public ilqr_malloc / ilqr_free and ilqr_host_alloc / ilqr_host_free.
+struct HipApi {
+  using Error = hipError_t;
+  using Event = hipEvent_t;
+  using Stream = hipStream_t;
+  static constexpr hipError_t ok = hipSuccess;
+  hipError_t dev_alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+  hipError_t dev_zero(void* p, size_t bytes) { return hipMemset(p, 0, bytes); }
+  void dev_free(void* p) { (void)hipFree(p); }
+  hipError_t pinned_alloc(void** p, size_t bytes, unsigned flags) { return hipHostMalloc(p, bytes, flags); }
+  void pinned_free(void* p) { (void)hipHostFree(p); }
+  hipError_t event_create(hipEvent_t* e, unsigned flags) { return hipEventCreateWithFlags(e, flags); }
+  void event_destroy(hipEvent_t e) { (void)hipEventDestroy(e); }
+  hipError_t stream_create(hipStream_t* s, unsigned flags) { return hipStreamCreateWithFlags(s, flags); }
+  void stream_destroy(hipStream_t s) { (void)hipStreamDestroy(s); }
+  void set_device(int device) { (void)hipSetDevice(device); }
+  void clear_last_error() { (void)hipGetLastError(); }
+};
+using HipOwned = Owned<HipApi>;
+
+// The one HIP error path: each family keeps its own thread-local text (its *_last_error entry
+// point reads it) and a one-line alias of ILQR_HIP_TRY on that text.
+inline ilqr_status hip_fail(std::string& text, hipError_t e, const char* what) {
+  text = std::string(what) + ": " + hipGetErrorString(e);
+  return ILQR_ERR_HIP;
+}
+#define ILQR_HIP_TRY(text, expr)                                      \
+  do {                                                                \
+    hipError_t e_ = (expr);                                           \
+    if (e_ != hipSuccess) return ilqr::hip_fail(text, e_, #expr);     \
+  } while (0)
 
 // Per-instance LQ problem data, device pointers, row-major, trajectory slowest.
 struct LQParams {

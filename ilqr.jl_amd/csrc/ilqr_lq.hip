@@ -1042,13 +1042,14 @@ hipError_t launch_count_running(int B, const int32_t* status, int32_t* out, hipS
 int run_selftest(int device) {
   if (hipSetDevice(device) != hipSuccess) return -1;
   int32_t* f = nullptr;
-  if (hipMalloc(&f, sizeof(int32_t)) != hipSuccess) return -1;
+  HipOwned tmp;  // the flag word, released on every exit
+  tmp.set_device(device);
+  tmp.dev_zero(&f, 1);
+  if (!tmp.ok()) return -1;
   int32_t h = 0;
-  if (hipMemset(f, 0, sizeof(int32_t)) != hipSuccess) return -1;
   selftest_kernel<<<1, 64>>>(f);
   if (hipGetLastError() != hipSuccess) return -1;
   if (hipMemcpy(&h, f, sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  (void)hipFree(f);
   return h;
 }
 

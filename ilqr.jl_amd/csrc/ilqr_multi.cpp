@@ -21,6 +21,9 @@ struct Shard {
   int device = 0;
   int b0 = 0, nb = 0;  // global trajectory range [b0, b0 + nb)
   ilqr_handle* h = nullptr;
+  // the resident arrays and the stream are acquired through `own` in ilqr_multi_create; the
+  // history scratch through `hist_own`, released and refilled when max_iter outgrows hcap
+  ilqr::HipOwned own, hist_own;
   double *A = nullptr, *B = nullptr, *Q = nullptr, *R = nullptr, *Qf = nullptr;
   double *x = nullptr, *u = nullptr, *xt = nullptr, *xo = nullptr, *uo = nullptr, *cost = nullptr;
   int32_t *iters = nullptr, *status = nullptr;
@@ -55,15 +58,10 @@ int severity(ilqr_status s) {  // which status the call reports when shards diff
 }
 
 void free_shard(Shard& s) {
-  if (s.h) ilqr_destroy(s.h);
-  (void)hipSetDevice(s.device);
-  for (double* p : {s.A, s.B, s.Q, s.R, s.Qf, s.x, s.u, s.xt, s.xo, s.uo, s.cost, s.hcost, s.halpha, s.hdu2})
-    (void)hipFree(p);
-  (void)hipFree(s.iters);
-  (void)hipFree(s.status);
-  (void)hipFree(s.htrials);
-  if (s.stream) (void)hipStreamDestroy(s.stream);
-  s = Shard{};
+  (void)ilqr_destroy(s.h);
+  s.h = nullptr;
+  s.hist_own.release();
+  s.own.release();
 }
 
 ilqr_status hip_status(hipError_t e) { return e == hipSuccess ? ILQR_OK : ILQR_ERR_HIP; }
@@ -185,7 +183,7 @@ ilqr_status ilqr_multi_create(ilqr_multi** out, const int* devices, int n_device
   m->nu = nu;
   m->T = T;
   m->batch = batch;
-  m->shards.resize(n_devices);
+  m->shards = std::vector<Shard>(n_devices);  // a Shard holds its owners: never moved
   ilqr_status st = ILQR_OK;
   for (int i = 0; i < n_devices && st == ILQR_OK; ++i) {
     Shard& s = m->shards[i];
@@ -194,26 +192,27 @@ ilqr_status ilqr_multi_create(ilqr_multi** out, const int* devices, int n_device
     s.nb = (int)((long long)batch * (i + 1) / n_devices) - s.b0;
     if (s.nb == 0) continue;
     if (hipSetDevice(s.device) != hipSuccess) { st = ILQR_ERR_HIP; break; }
-    if (hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) != hipSuccess) { st = ILQR_ERR_HIP; break; }
+    s.own.set_device(s.device);
+    s.hist_own.set_device(s.device);
+    s.own.stream(&s.stream, hipStreamNonBlocking);
+    if (!s.own.ok()) { st = ILQR_ERR_HIP; break; }
     if ((st = ilqr_create(&s.h, s.device, nx, nu, T, s.nb)) != ILQR_OK) break;
     if ((st = ilqr_set_stream(s.h, s.stream)) != ILQR_OK) break;
     const size_t nb = (size_t)s.nb, xs = (size_t)(T + 1) * nx, us = (size_t)T * nu;
-    hipError_t e = hipSuccess;
-    auto al = [&](auto** q, size_t n) { if (e == hipSuccess) e = hipMalloc(q, sizeof(**q) * n); };
-    al(&s.A, nb * nx * nx);
-    al(&s.B, nb * nx * nu);
-    al(&s.Q, nb * nx * nx);
-    al(&s.R, nb * nu * nu);
-    al(&s.Qf, nb * nx * nx);
-    al(&s.x, nb * xs);
-    al(&s.xt, nb * xs);
-    al(&s.xo, nb * xs);
-    al(&s.u, nb * us);
-    al(&s.uo, nb * us);
-    al(&s.cost, nb);
-    al(&s.iters, nb);
-    al(&s.status, nb);
-    if (e != hipSuccess) st = ILQR_ERR_HIP;
+    s.own.dev(&s.A, nb * nx * nx);
+    s.own.dev(&s.B, nb * nx * nu);
+    s.own.dev(&s.Q, nb * nx * nx);
+    s.own.dev(&s.R, nb * nu * nu);
+    s.own.dev(&s.Qf, nb * nx * nx);
+    s.own.dev(&s.x, nb * xs);
+    s.own.dev(&s.xt, nb * xs);
+    s.own.dev(&s.xo, nb * xs);
+    s.own.dev(&s.u, nb * us);
+    s.own.dev(&s.uo, nb * us);
+    s.own.dev(&s.cost, nb);
+    s.own.dev(&s.iters, nb);
+    s.own.dev(&s.status, nb);
+    if (!s.own.ok()) st = ILQR_ERR_HIP;
   }
   if (st != ILQR_OK) {
     g_multi_error = "ilqr_multi_create failed on a device";
@@ -283,17 +282,17 @@ ilqr_status ilqr_multi_fit_resident(ilqr_multi* m, const ilqr_options* o, int fl
     for (Shard& s : m->shards) {
       if (s.nb == 0 || s.hcap >= max_iter) continue;
       if (hipSetDevice(s.device) != hipSuccess) return ILQR_ERR_HIP;
-      for (double* q : {s.hcost, s.halpha, s.hdu2}) (void)hipFree(q);
-      (void)hipFree(s.htrials);
-      s.hcost = s.halpha = s.hdu2 = nullptr;
-      s.htrials = nullptr;
+      s.hist_own.release();
       s.hcap = 0;
       const size_t n = (size_t)max_iter * s.nb;
-      hipError_t e = hipMalloc(&s.hcost, sizeof(double) * n);
-      if (e == hipSuccess) e = hipMalloc(&s.halpha, sizeof(double) * n);
-      if (e == hipSuccess) e = hipMalloc(&s.hdu2, sizeof(double) * n);
-      if (e == hipSuccess) e = hipMalloc(&s.htrials, sizeof(int32_t) * n);
-      if (e != hipSuccess) return ILQR_ERR_HIP;
+      s.hist_own.dev(&s.hcost, n);
+      s.hist_own.dev(&s.halpha, n);
+      s.hist_own.dev(&s.hdu2, n);
+      s.hist_own.dev(&s.htrials, n);
+      if (!s.hist_own.ok()) {
+        s.hist_own.release();  // the next call starts again from nothing
+        return ILQR_ERR_HIP;
+      }
       s.hcap = max_iter;
     }
   }
