@@ -1624,8 +1624,41 @@ ilqr_status ilqr_chain_set_task_targets(ilqr_chain_handle* h, const double* targ
   return chain_set_goal_rows(h, targets, 3, &h->tiles.task_rows, &h->tiles.task_rows_on, "ilqr_chain_set_task_targets");
 }
 
+// The path as chain_set_goal_rows takes its rows — the handle's own buffers, acquired at the
+// first call and kept, filled by device-to-device copies on the handle's stream and waited
+// for — plus the compact copy of the rows T that the goal-row kernels read. lxx is written by
+// every backward while the path applies, so clearing it in a task mode restores the mode's
+// constant Hessian tiles (a change of the cost mode does that itself).
+ilqr_status ilqr_chain_set_task_path(ilqr_chain_handle* h, const double* path, double path_weight) {
+  if (!h) return ILQR_ERR_BAD_ARG;
+  if (!on_tiles(h)) {
+    g_chain_error = "ilqr_chain_set_task_path: needs a handle that iterates on the tiles path (4 to 7 joints, fp64)";
+    return ILQR_ERR_UNSUPPORTED;
+  }
+  ilqr_chain_handle::Tiles& t = h->tiles;
+  if (!path) {
+    if (!t.path_on) return ILQR_OK;
+    t.path_on = false;
+    if (!h->task_mode()) return ILQR_OK;
+    CH_TRY(hipSetDevice(h->device));
+    CH_TRY(tiles_table(h)->hessians(h));
+    return ILQR_OK;
+  }
+  if (!std::isfinite(path_weight)) return ILQR_ERR_BAD_ARG;
+  const size_t B = (size_t)h->batch, row = 3 * sizeof(double), traj = row * ((size_t)h->T + 1);
+  CH_TRY(hipSetDevice(h->device));
+  CH_TRY(chain_lazy_dev(h, &t.path, B * ((size_t)h->T + 1) * 3));
+  CH_TRY(chain_lazy_dev(h, &t.path_goal, B * 3));
+  CH_TRY(hipMemcpyAsync(t.path, path, B * traj, hipMemcpyDeviceToDevice, h->stream));
+  CH_TRY(hipMemcpy2DAsync(t.path_goal, row, path + 3 * (size_t)h->T, traj, row, B, hipMemcpyDeviceToDevice, h->stream));
+  CH_TRY(hipStreamSynchronize(h->stream));
+  t.path_weight = path_weight;
+  t.path_on = true;
+  return ILQR_OK;
+}
+
 int32_t ilqr_chain_get_target_mode(const ilqr_chain_handle* h) {
-  return h ? (h->tiles.joint_rows_on ? 1 : 0) | (h->tiles.task_rows_on ? 2 : 0) : -1;
+  return h ? (h->tiles.joint_rows_on ? 1 : 0) | (h->tiles.task_rows_on ? 2 : 0) | (h->tiles.path_on ? 4 : 0) : -1;
 }
 
 int32_t ilqr_chain_get_dynamics(const ilqr_chain_handle* h) {

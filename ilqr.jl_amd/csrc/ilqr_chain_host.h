@@ -15,7 +15,8 @@ struct ilqr_chain_handle {
   ilqr_chain chain{};
   hipStream_t stream = nullptr;
   // every device buffer, pinned word and event below is acquired through `own`: in
-  // ilqr_chain_create, or at its first use (two.task_dev, tiles.joint_rows, tiles.task_rows)
+  // ilqr_chain_create, or at its first use (two.task_dev, tiles.joint_rows, tiles.task_rows,
+  // tiles.path, tiles.path_goal)
   ilqr::HipOwned own;
   void* xbuf[2] = {nullptr, nullptr};
   void* ubuf[2] = {nullptr, nullptr};
@@ -57,9 +58,18 @@ struct ilqr_chain_handle {
     // kept; `on` while an override is set. Each applies while its cost family is in effect.
     double *joint_rows = nullptr, *task_rows = nullptr;
     bool joint_rows_on = false, task_rows_on = false;
+    // a tool path (ilqr_chain_set_task_path): the handle's copy of the (batch, T + 1, 3) rows,
+    // a compact (batch, 3) copy of the rows T — trajectory b's final_target while the path is
+    // set, handed to the kernels that read a goal row in place of task_rows — and the running
+    // weight; allocated at the first call and kept. Applies while a task mode is in effect.
+    double *path = nullptr, *path_goal = nullptr;
+    double path_weight = 0.0;
+    bool path_on = false;
     const double* goal_rows(bool task_mode) const {
-      return task_mode ? (task_rows_on ? task_rows : nullptr) : (joint_rows_on ? joint_rows : nullptr);
+      if (task_mode) return path_on ? path_goal : (task_rows_on ? task_rows : nullptr);
+      return joint_rows_on ? joint_rows : nullptr;
     }
+    const double* path_rows(bool task_mode) const { return task_mode && path_on ? path : nullptr; }
   } tiles;
 };
 

@@ -666,6 +666,59 @@ __global__ __launch_bounds__(64) void chain_task_quad_kernel(ChainK<double, NJ> 
   }
 }
 
+// A tool path (ilqr_chain_set_task_path): the handle's copy of the (batch, T + 1, 3) rows and
+// the running weight. While it is set and a task mode is in effect the stage cost is
+// ℓ_t = Σū² + w · Σₖ (πₖ(q) − rows[b, t, k])², π the mode's reading of the point
+// (chain_task_value); row T is trajectory b's final_target, which the kernels that read a
+// goal get as the handle's compact copy of those rows (ChainGoalRows).
+struct ChainPath {
+  const double* rows;
+  double w;
+};
+template <class X, class... A>
+constexpr int pack_count = (0 + ... + (std::is_same_v<A, X> ? 1 : 0));
+__device__ __forceinline__ const ChainPath& path_of(const ChainGoalRows&, const ChainPath& p) { return p; }
+__device__ __forceinline__ const double* goal_rows(const ChainGoalRows& g, const ChainPath&) { return g.rows; }
+
+// The per-step tiles of the path cost, one lane per (b, t < T): the quadratization of
+// w · Σₖ (πₖ(q) − rows[b, t, k])² at x[b, t] (chain_task_quad_fk on a ChainTaskK whose target
+// is the step's row and whose weight is the path's) as the joint rows of lx[b, t] —
+// chain_cost_tiles_kernel, which runs before, wrote the velocity rows (0) and lu = 2u — and
+// the whole lxx[b, t] tile: i ≤ j computed and mirrored, so exactly symmetric, velocity rows
+// and columns exactly 0. Trajectories whose status is not OK are skipped like that kernel's.
+template <int NJ>
+__global__ __launch_bounds__(64) void chain_path_tiles_kernel(ChainK<double, NJ> P, ChainTaskK C, ChainPath path, int B,
+                                                              int T, const double* __restrict__ x,
+                                                              const int32_t* __restrict__ status,
+                                                              double* __restrict__ lx, double* __restrict__ lxx) {
+  constexpr int NX = 2 * NJ;
+  const size_t bt = (size_t)blockIdx.x * 64 + threadIdx.x;
+  if (bt >= (size_t)B * T) return;
+  const int b = (int)(bt / T), t = (int)(bt - (size_t)b * T);
+  if (status && status[b] != ILQR_TRAJ_OK) return;
+  const size_t row = (size_t)b * (T + 1) + t;
+  const double* xb = x + row * NX;
+  double q[NJ], c, g[NJ], H[NJ][NJ];
+#pragma unroll
+  for (int i = 0; i < NJ; ++i) q[i] = xb[i];
+  ChainTaskK Cp = C;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) Cp.t[k] = path.rows[row * 3 + k];
+  Cp.w = path.w;
+  chain_task_quad_fk<NJ>(P, Cp, q, c, g, H);
+  double* go = lx + bt * NX;
+#pragma unroll
+  for (int i = 0; i < NJ; ++i) go[i] = g[i];
+  double* ho = lxx + bt * NX * NX;
+#pragma unroll
+  for (int i = 0; i < NX; ++i)
+#pragma unroll
+    for (int j = 0; j < NX; ++j) {
+      const int lo = i < j ? i : j, hi = i < j ? j : i;
+      ho[i * NX + j] = hi < NJ ? H[lo][hi] : 0.0;
+    }
+}
+
 // Forward rollout + α-halving line search of a chain on the tiles path: chain_forward_lane's
 // arithmetic in its order, every lane of a 32-lane group carrying the same x̄, ū, cost and
 // Σδu² (the dynamics split over the group: chain_xdot_cv32).
@@ -696,6 +749,12 @@ static_assert(ChainStage<7, 7>::WORDS == 5 && ChainStage<7, 7>::SIZE == 160, "se
 // the first NG of those words read the row instead (stride 0) and the hand-off delivers it
 // to the group at stage[N_IN ..) — no register beyond what the shared-goal code holds, which
 // at seven joints already fills both register files.
+// A tool path (Goal = ChainGoalRows, ChainPath; TASK and ROWS both set, the row being the
+// path's row T): every step adds chain_task_value of the step's path row at the point of q̄_t
+// to chain_task_stage(ū), every lane of the group on its own copy of x̄_t by the same code,
+// as the terminal cost. Step t's row rides in the tail too, three words behind the goal row
+// at stage[N_IN + NG ..) with stride 3, prefetched one step ahead with the record. The
+// kinematics sit before the RK4 step, so their temporaries are dead at its stages.
 template <int NJ, int NU, bool TASK = false, bool ROWS = false, class... Goal>
 __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P, double* __restrict__ stage,
                                                      int b, int T, const double* __restrict__ x,
@@ -707,15 +766,18 @@ __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P
                                                      double* du2_out, const LSParams& ls,
                                                      const ChainTaskK& C = ChainTaskK{}, const Goal&... G) {
   using V = double;
-  static_assert((std::is_same_v<Goal, ChainGoalRows> && ...) && sizeof...(Goal) == (ROWS ? 1 : 0),
+  constexpr bool PATH = pack_count<ChainPath, Goal...> == 1;
+  static_assert(pack_count<ChainGoalRows, Goal...> == (ROWS ? 1 : 0) && sizeof...(Goal) == (ROWS ? 1 : 0) + (PATH ? 1 : 0),
                 "Goal: ChainGoalRows with ROWS, else none (the shared-goal instantiations keep their signature)");
+  static_assert(!PATH || (TASK && ROWS), "Goal: ChainGoalRows, ChainPath in a task mode with a path");
   constexpr int NX = 2 * NJ, NK = NU * NX;
   constexpr int O_X = NK, O_XT = O_X + NX, O_U = O_XT + NJ, O_D = O_U + NU, N_IN = O_D + NU;
   constexpr int NW = ChainStage<NJ, NU>::WORDS;
   static_assert(N_IN == ChainStage<NJ, NU>::N_IN && N_IN <= ChainStage<NJ, NU>::SIZE && NX + NU <= CH32_LANES,
                 "a step's inputs in NW words per lane, x̄ and ū stored by one lane each");
   constexpr int NG = ROWS ? (TASK ? 3 : NJ) : 0, O_G = N_IN;  // the goal row in the stage's tail
-  static_assert(N_IN + NG <= ChainStage<NJ, NU>::SIZE, "the goal row fits the stage's unused tail");
+  constexpr int NP = PATH ? 3 : 0, O_P = O_G + NG;  // the step's path row behind it
+  static_assert(N_IN + NG + NP <= ChainStage<NJ, NU>::SIZE, "the goal row and the path row fit the stage's unused tail");
   const int l32 = threadIdx.x & (CH32_LANES - 1);
   const V* xb0 = x + (size_t)b * (T + 1) * NX;
   const V* ub0 = u + (size_t)b * T * NU;
@@ -740,6 +802,11 @@ __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P
     else if (e < N_IN) { src[k] = d0 + (e - O_D); str[k] = NU; }
     else if constexpr (ROWS) {  // stride 0: the row at every step
       if (e < O_G + NG) src[k] = goal_rows(G...) + (size_t)b * NG + (e - O_G);
+      if constexpr (PATH)
+        if (e >= O_P && e < O_P + NP) {
+          src[k] = path_of(G...).rows + (size_t)b * (T + 1) * 3 + (e - O_P);
+          str[k] = 3;
+        }
     }
   }
   V alpha = V(ls.alpha0);
@@ -782,6 +849,17 @@ __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P
       V lk = V(0);
       if constexpr (TASK) {
         lk = chain_task_stage<NU>(ubar);  // ignores x and x_traj (cost_functions.jl:45-51)
+        if constexpr (PATH) {  // … + w Σₖ (πₖ(q̄ₖ) − row_k)², the hand-off left the step's row
+          V q[NJ], pw[3];
+#pragma unroll
+          for (int i = 0; i < NJ; ++i) q[i] = xb[i];
+          chain_point_fk<NJ>(P, C, q, pw);
+          ChainTaskK Cp = C;
+#pragma unroll
+          for (int k = 0; k < 3; ++k) Cp.t[k] = stage[O_P + k];
+          Cp.w = path_of(G...).w;
+          lk = lk + chain_task_value(Cp, pw);
+        }
       } else {
 #pragma unroll
         for (int i = 0; i < NJ; ++i) {
@@ -880,11 +958,10 @@ constexpr int CH32_WG = 64;  // two trajectories per workgroup (one wave)
 // pointer one more argument). As a pack it adds nothing to the joint-cost kernels' argument
 // list, so every mode keeps the kernel arguments, and with them the code, that each had as a
 // kernel written out. A pack in the middle of the list is never deduced: every launch spells
-// out <NJ, NU>, <NJ, NU, ChainTaskK>, <NJ, NU, ChainGoalRows> or
-// <NJ, NU, ChainTaskK, ChainGoalRows>.
-template <class X, class... A>
-constexpr int pack_count = (0 + ... + (std::is_same_v<A, X> ? 1 : 0));
-// none | ChainTaskK | ChainGoalRows | ChainTaskK, ChainGoalRows
+// out <NJ, NU>, <NJ, NU, ChainTaskK>, <NJ, NU, ChainGoalRows>,
+// <NJ, NU, ChainTaskK, ChainGoalRows> or <NJ, NU, ChainTaskK, ChainGoalRows, ChainPath> (a tool
+// path: the goal rows are then the path's rows T).
+// none | ChainTaskK | ChainGoalRows | ChainTaskK, ChainGoalRows | ChainTaskK, ChainGoalRows, ChainPath
 template <class... A>
 struct CostPack : std::false_type {};
 template <>
@@ -895,13 +972,15 @@ template <>
 struct CostPack<ChainGoalRows> : std::true_type {};
 template <>
 struct CostPack<ChainTaskK, ChainGoalRows> : std::true_type {};
+template <>
+struct CostPack<ChainTaskK, ChainGoalRows, ChainPath> : std::true_type {};
 template <int NJ, int NU, class... TaskK>
 __global__ __launch_bounds__(CH32_WG) void chain_forward32_kernel(
     ChainK<double, NJ> P, TaskK... C, int B, int T, const double* __restrict__ x, const double* __restrict__ u,
     const double* __restrict__ xtraj, const double* __restrict__ d, const double* __restrict__ K,
     const double* __restrict__ prev_cost, double* __restrict__ xnew, double* __restrict__ unew,
     double* __restrict__ new_cost, int32_t* __restrict__ trials, int32_t* __restrict__ status, LSParams ls) {
-  static_assert(CostPack<TaskK...>::value, "TaskK: none or ChainTaskK, then none or ChainGoalRows");
+  static_assert(CostPack<TaskK...>::value, "TaskK: none or ChainTaskK, then none or ChainGoalRows, then none or ChainPath");
   static_assert(kernarg_bytes<ChainK<double, NJ>, TaskK..., int, int, const double*, const double*, const double*,
                               const double*, const double*, const double*, double*, double*, double*, int32_t*,
                               int32_t*, LSParams>() <= HIP_KERNARG_LIMIT,
@@ -930,7 +1009,7 @@ __global__ __launch_bounds__(CH32_WG) void chain_iter_forward32_kernel(ChainK<do
                                                                      ChainIter<double> a,
                                                                      const int32_t* __restrict__ bstatus,
                                                                      LSParams ls) {
-  static_assert(CostPack<TaskK...>::value, "TaskK: none or ChainTaskK, then none or ChainGoalRows");
+  static_assert(CostPack<TaskK...>::value, "TaskK: none or ChainTaskK, then none or ChainGoalRows, then none or ChainPath");
   static_assert(kernarg_bytes<ChainK<double, NJ>, TaskK..., int, int, ChainIter<double>, const int32_t*,
                               LSParams>() <= HIP_KERNARG_LIMIT,
                 "the chain constants by value: the argument block within HIP's limit");
@@ -983,14 +1062,18 @@ struct ChainTilesOps {
     return C;
   }
   // fn(the extra kernel arguments of a cost pack...): ChainTaskK in a task mode (TASKK: of
-  // the kernels that take it as part of the pack), then ChainGoalRows when `rows` is set. Each
+  // the kernels that take it as part of the pack), then ChainGoalRows when `rows` is set, then
+  // ChainPath while a tool path applies (those kernels only; `rows` is then its rows T). Each
   // launch names its pack from these arguments' types, so a kernel is instantiated for the
   // packs its callers can reach and no other (the comment above CostPack).
   template <bool TASKK, class Fn>
   static hipError_t with_cost_pack(const ilqr_chain_handle* h, const double* rows, Fn&& fn) {
     const ilqr::ChainGoalRows g{rows};
     if constexpr (TASKK)
-      if (h->task_mode()) return rows ? fn(h->tiles.taskk, g) : fn(h->tiles.taskk);
+      if (h->task_mode()) {
+        if (const double* p = h->tiles.path_rows(true)) return fn(h->tiles.taskk, g, ilqr::ChainPath{p, h->tiles.path_weight});
+        return rows ? fn(h->tiles.taskk, g) : fn(h->tiles.taskk);
+      }
     return rows ? fn(g) : fn();
   }
   // a goal per trajectory of the cost in effect, or null
@@ -1039,7 +1122,14 @@ struct ChainTilesOps {
       return hipGetLastError();
     });
     if (e != hipSuccess || !h->task_mode()) return e;
-    // a task mode: lx = 0 and lu = 2u came from the weights above; the terminal tiles from x_N
+    // a task mode: lx = 0 and lu = 2u came from the weights above; with a tool path the joint
+    // rows of lx and the lxx tiles from the steps' rows; the terminal tiles from x_N
+    if (const double* p = t.path_rows(true)) {
+      const size_t np = (size_t)h->batch * h->T;
+      ilqr::chain_path_tiles_kernel<NJ><<<(unsigned)((np + 63) / 64), 64, 0, h->stream>>>(
+          chain_consts<V, NJ>(h->chain), t.taskk, ilqr::ChainPath{p, t.path_weight}, h->batch, h->T, x, st, t.lx, t.lxx);
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
     return quadratize(h, x + (size_t)h->T * NX, (size_t)(h->T + 1) * NX, h->batch, st, nullptr, t.lfx, t.lfxx);
   }
   // final_cost_quadratization of the cost in effect at n states x[s·stride .. +NX); with a

@@ -66,6 +66,7 @@ CHAIN_COST_SIMPLE = 1
 CHAIN_COST_SIMPLE_EUCLIDEAN = 2
 CHAIN_TARGETS_JOINT = 1         # ilqr_chain_get_target_mode's bits: goals per trajectory
 CHAIN_TARGETS_TASK = 2
+CHAIN_TARGETS_PATH = 4          # a tool path (ilqr_chain_set_task_path)
 CHAIN_MAX_JOINTS = 8
 
 
@@ -181,6 +182,7 @@ SIGNATURES = {
     "ilqr_chain_get_cost_mode": (C.c_int32, [P]),
     "ilqr_chain_set_joint_targets": (C.c_int, [P, P]),
     "ilqr_chain_set_task_targets": (C.c_int, [P, P]),
+    "ilqr_chain_set_task_path": (C.c_int, [P, P, C.c_double]),
     "ilqr_chain_get_target_mode": (C.c_int32, [P]),
     "ilqr_chain_sync": (C.c_int, [P]),
     "ilqr_chain_dynamics": (C.c_int, [P, P, P, P, C.c_int]),

@@ -351,18 +351,35 @@ class ChainSolver:
         None restores it. Copy semantics as set_joint_targets."""
         self._set_targets(self.lib.ilqr_chain_set_task_targets, "ilqr_chain_set_task_targets", targets, 3)
 
+    def set_task_path(self, path, weight: float = 0.0):
+        """A tool path per trajectory (ilqr_chain_set_task_path; four to seven joints, fp64): a
+        float64 CUDA tensor, or a host array, of shape (batch, T + 1, 3). While it is set and a
+        task reading of set_simple_costs is in effect, step t < T of trajectory b costs
+        Σ uᵢ² + weight·Σₖ (πₖ − path[b, t, k])² (π the reading's point: p, or p_z for every k)
+        and row T replaces final_target (and set_task_targets' row b) in ℓ_f. x_traj stays
+        ignored by the task costs. None clears the path (weight is then not read). Copy
+        semantics as set_joint_targets."""
+        if path is not None:
+            if not isinstance(path, torch.Tensor):
+                path = torch.as_tensor(np.ascontiguousarray(path), device=self.dev)
+            _req(path, torch.float64, (self.batch, self.T + 1, 3), "path")
+        self._bind()   # the rows are copied, and the cleared mode's tiles enqueued, on the handle's stream
+        _lib.check(self.lib.ilqr_chain_set_task_path(self.h, _ptr(path), float(weight)), "ilqr_chain_set_task_path")
+
     @property
     def target_mode(self) -> frozenset:
-        """Which goals are per trajectory: a subset of {"joint", "task"}."""
+        """Which goals are per trajectory: a subset of {"joint", "task", "path"}."""
         m = int(self.lib.ilqr_chain_get_target_mode(self.h))
-        return frozenset(k for k, bit in (("joint", _lib.CHAIN_TARGETS_JOINT), ("task", _lib.CHAIN_TARGETS_TASK))
+        return frozenset(k for k, bit in (("joint", _lib.CHAIN_TARGETS_JOINT), ("task", _lib.CHAIN_TARGETS_TASK),
+                                          ("path", _lib.CHAIN_TARGETS_PATH))
                          if m & bit)
 
     def final_cost_quadratization(self, x):
         """final_cost_quadratization (backward_pass.jl:134-153) of the cost in effect at the
         states x (n, nx): (ℓ_f (n,), ∇ℓ_f (n, nx), ∇²ℓ_f (n, nx, nx)) on the device
         (ilqr_chain_final_cost_quadratize: four to seven joints, fp64). With goals per
-        trajectory of the mode in effect, state s is paired with goal s and n must be batch."""
+        trajectory of the mode in effect (a tool path's rows T among them), state s is paired
+        with goal s and n must be batch."""
         n = x.shape[0]
         _req(x, torch.float64, (n, self.nx), "x")
         cost = self._new(n, dtype=torch.float64)

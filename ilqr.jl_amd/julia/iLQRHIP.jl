@@ -918,6 +918,7 @@ mutable struct ChainSolver
     x::Ptr{Cvoid}; u::Ptr{Cvoid}; xo::Ptr{Cvoid}; uo::Ptr{Cvoid}; status::Ptr{Int32}
     lock::ReentrantLock
     nj::Int; nb::Int         # joints and batch: the shape of a goal per trajectory
+    T::Int                   # the horizon: a tool path has T + 1 rows
 end
 
 function ChainSolver(c::Chain, nx::Integer, nu::Integer, T::Integer, nb::Integer, ::Type{E}, linearization,
@@ -953,7 +954,7 @@ function ChainSolver(c::Chain, nx::Integer, nu::Integer, T::Integer, nb::Integer
     h = Handle(nx, nu, T, 1; device=device)  # device-memory helper only
     a(n) = Ptr{Cvoid}(alloc(h, E, n))
     s = ChainSolver(r[], h, a(nb * (T + 1) * nx), a(nb * T * nu), a(nb * (T + 1) * nx), a(nb * T * nu),
-                    alloc(h, Int32, nb), ReentrantLock(), Int(c.n_joints), Int(nb))
+                    alloc(h, Int32, nb), ReentrantLock(), Int(c.n_joints), Int(nb), Int(T))
     finalizer(destroy!, s)      # a backstop; close(s) frees everything at once
     return s
 end
@@ -998,6 +999,29 @@ set_task_targets!(s::ChainSolver, targets::Union{Nothing,Matrix{Float64}}) =
     set_targets!(s, "ilqr_chain_set_task_targets", targets, 3) do p
         ccall((:ilqr_chain_set_task_targets, libilqr), Cint, (Ptr{Cvoid}, Ptr{Float64}), s.ch, p)
     end
+
+"""set_task_path!(s, path, weight): a tool path per trajectory, `path` (3, T+1, batch) — the same
+bytes as the C ABI's (batch, T+1, 3). While it is set and a task reading of simple_costs is in
+effect, step t of trajectory b costs Σu² + weight·Σₖ(πₖ − path[k, t, b])² and column T+1
+replaces final_target; `nothing` clears the path."""
+function set_task_path!(s::ChainSolver, path::Union{Nothing,Array{Float64,3}}, weight::Real=0.0)
+    what = "ilqr_chain_set_task_path"
+    set(p) = ccall((:ilqr_chain_set_task_path, libilqr), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cdouble), s.ch, p,
+                   Float64(weight))
+    if path === nothing
+        check(set(Ptr{Float64}(C_NULL)), what)
+        return s
+    end
+    size(path) == (3, s.T + 1, s.nb) ||
+        throw(DimensionMismatch("$what: expected (3, $(s.T + 1), $(s.nb)), got $(size(path))"))
+    p = upload(s.h, path)
+    try
+        check(set(p), what)
+    finally
+        release!(s.h, p)
+    end
+    return s
+end
 
 target_mode(s::ChainSolver) = ccall((:ilqr_chain_get_target_mode, libilqr), Int32, (Ptr{Cvoid},), s.ch)
 

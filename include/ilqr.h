@@ -402,7 +402,9 @@ ilqr_status ilqr_fit_ex(ilqr_handle* h, const ilqr_problem* p, const ilqr_option
  * doubles — plus, for both, the gains (nu·nx + nu) and two trajectory buffers (2(nx + nu)):
  * 2nx² + 2nx·nu + nu² + 3nx + 4nu doubles on the tiles path, which with nx = 2n, nu = n is
  * 13n² + 10n — 248, 375, 528 and 707 doubles (1984, 3000, 4224 and 5656 bytes) per
- * (trajectory, step) for 4, 5, 6 and 7 joints.
+ * (trajectory, step) for 4, 5, 6 and 7 joints. A tool path (ilqr_chain_set_task_path) adds,
+ * from its first call on, its rows: 3(T + 1) doubles per trajectory and 3 for the compact copy
+ * of the rows T.
  * --------------------------------------------------------------------------- */
 #define ILQR_CHAIN_MAX_JOINTS 8
 
@@ -549,8 +551,40 @@ int32_t ilqr_chain_get_cost_mode(const ilqr_chain_handle* h);
  * ILQR_ERR_UNSUPPORTED with a sentence in ilqr_chain_last_error. */
 ilqr_status ilqr_chain_set_joint_targets(ilqr_chain_handle* h, const double* targets);
 ilqr_status ilqr_chain_set_task_targets(ilqr_chain_handle* h, const double* targets);
-/* bit 0: joint targets per trajectory, bit 1: task targets per trajectory; −1 for a NULL
- * handle */
+/* A tool path, for handles that iterate on the tiles path (4 to 7 joints, fp64): where the
+ * point of ilqr_chain_set_task_costs should be on the way to its goal. With a path set and a
+ * task mode in effect trajectory b minimises, for t = 0 … T − 1,
+ *   ℓ_t(x, u) = Σₐ uₐ² + path_weight · Σₖ (πₖ(q) − path[b, t, k])²
+ *   ℓ_f(x_T)  = weight · Σₖ (πₖ(q_T) − path[b, T, k])²
+ * with q = x[0:n_joints] and π the mode's reading of the point's position: πₖ = pₖ under
+ * ILQR_CHAIN_COST_SIMPLE_EUCLIDEAN, πₖ = p_z for every k under ILQR_CHAIN_COST_SIMPLE (the
+ * reading its terminal cost has). weight, body and point stay those of
+ * ilqr_chain_set_task_costs; x_traj stays ignored by the task costs. Row T of the path is
+ * trajectory b's final_target while the path is set: it takes precedence over
+ * ilqr_chain_set_task_costs' final_target and over ilqr_chain_set_task_targets' rows, which
+ * come back when the path is cleared.
+ * path: (batch, T + 1, 3) device doubles, NULL clears it (path_weight is then not read). The
+ * rows are copied into buffers the handle owns (allocated at the first call, reused
+ * afterwards: 3(T + 1) + 3 doubles per trajectory) by device-to-device copies on the handle's
+ * stream, which the call waits for: the caller may overwrite or free its array when the call
+ * returns, and a further call replaces the rows without allocating. The path stays until it
+ * is cleared and applies whenever a task mode is in effect; it is inert in
+ * ILQR_CHAIN_COST_JOINT, and ilqr_chain_set_task_costs neither drops nor needs it. backward,
+ * forward, iterate, fit and fit_ex honour it with every linearisation;
+ * ilqr_chain_final_cost_quadratize, with a path in effect, pairs state s with path[s, T] and
+ * then requires n == batch (ILQR_ERR_BAD_DIMS otherwise). The per-step Hessian tiles depend
+ * on the state while a path applies; clearing it, like every change of the cost mode,
+ * enqueues the mode's constant ones on the handle's stream. A handle without a path launches
+ * the kernels it launched before this entry point existed.
+ * The rows are NOT validated: a NaN in trajectory b's path ends b alone, through
+ * ILQR_TRAJ_NAN.
+ * Returns, before any device call: NULL handle → ILQR_ERR_BAD_ARG; a handle that does not
+ * iterate on the tiles path (any 2-joint chain, 4 to 7 joints in ILQR_F32) →
+ * ILQR_ERR_UNSUPPORTED with a sentence in ilqr_chain_last_error; a non-finite path_weight
+ * with a path → ILQR_ERR_BAD_ARG, the handle's state unchanged. */
+ilqr_status ilqr_chain_set_task_path(ilqr_chain_handle* h, const double* path, double path_weight);
+/* bit 0: joint targets per trajectory, bit 1: task targets per trajectory, bit 2: a tool
+ * path; −1 for a NULL handle */
 int32_t ilqr_chain_get_target_mode(const ilqr_chain_handle* h);
 ilqr_status ilqr_chain_sync(ilqr_chain_handle* h);
 /* dynamicsf for n independent (x, u) pairs: x (n, nx), u (n, nu) → x_next (n, nx) */
