@@ -1657,6 +1657,42 @@ ilqr_status ilqr_chain_set_task_path(ilqr_chain_handle* h, const double* path, d
   return ILQR_OK;
 }
 
+// Joint-velocity weights: host values the launches take by value, in stream order. lxx and
+// lfxx carry them on the velocity diagonal, so setting, replacing and clearing enqueue the
+// Hessian tiles of the cost in effect as a change of the cost mode does (with a tool path in
+// effect every backward rewrites lxx anyway).
+ilqr_status ilqr_chain_set_velocity_weights(ilqr_chain_handle* h, const double* v_weight, const double* vf_weight) {
+  if (!h) return ILQR_ERR_BAD_ARG;
+  if (!on_tiles(h)) {
+    g_chain_error =
+        "ilqr_chain_set_velocity_weights: needs a handle that iterates on the tiles path (4 to 7 joints, fp64)";
+    return ILQR_ERR_UNSUPPORTED;
+  }
+  for (int i = 0; i < h->nj; ++i)
+    if ((v_weight && !std::isfinite(v_weight[i])) || (vf_weight && !std::isfinite(vf_weight[i])))
+      return ILQR_ERR_BAD_ARG;
+  ilqr_chain_handle::Tiles& t = h->tiles;
+  const bool on = v_weight || vf_weight;
+  if (!on && !t.vel_on) return ILQR_OK;
+  for (int i = 0; i < ILQR_CHAIN_MAX_JOINTS; ++i) {
+    t.v_weight[i] = v_weight && i < h->nj ? v_weight[i] : 0.0;
+    t.vf_weight[i] = vf_weight && i < h->nj ? vf_weight[i] : 0.0;
+  }
+  t.vel_on = on;
+  CH_TRY(hipSetDevice(h->device));
+  CH_TRY(tiles_table(h)->hessians(h));
+  return ILQR_OK;
+}
+
+int32_t ilqr_chain_get_velocity_weights(const ilqr_chain_handle* h, double* v_weight, double* vf_weight) {
+  if (!h) return -1;
+  for (int i = 0; i < h->nj; ++i) {
+    if (v_weight) v_weight[i] = h->tiles.vel_on ? h->tiles.v_weight[i] : 0.0;
+    if (vf_weight) vf_weight[i] = h->tiles.vel_on ? h->tiles.vf_weight[i] : 0.0;
+  }
+  return h->tiles.vel_on ? 1 : 0;
+}
+
 int32_t ilqr_chain_get_target_mode(const ilqr_chain_handle* h) {
   return h ? (h->tiles.joint_rows_on ? 1 : 0) | (h->tiles.task_rows_on ? 2 : 0) | (h->tiles.path_on ? 4 : 0) : -1;
 }

@@ -70,6 +70,11 @@ struct ilqr_chain_handle {
       return joint_rows_on ? joint_rows : nullptr;
     }
     const double* path_rows(bool task_mode) const { return task_mode && path_on ? path : nullptr; }
+    // joint-velocity weights (ilqr_chain_set_velocity_weights): plain host values, handed to
+    // the kernels by value while `vel_on`; they own no device memory and apply in every cost
+    // mode, with or without goal rows and a path.
+    double v_weight[ILQR_CHAIN_MAX_JOINTS] = {}, vf_weight[ILQR_CHAIN_MAX_JOINTS] = {};
+    bool vel_on = false;
   } tiles;
 };
 

@@ -412,12 +412,31 @@ struct ChainGoalRows {
   const double* rows;
 };
 __device__ __forceinline__ const double* goal_rows(const ChainGoalRows& g) { return g.rows; }
+template <class X, class... A>
+constexpr int pack_count = (0 + ... + (std::is_same_v<A, X> ? 1 : 0));
+
+// Joint-velocity weights (ilqr_chain_set_velocity_weights): ℓ_t += Σ vwᵢ q̇ᵢ², ℓ_f += Σ vfwᵢ q̇ᵢ²
+// at T, q̇ᵢ = x[NJ + i], in every cost mode. One more trailing pack type, always the last and
+// by value: empty for a handle without weights, whose instantiations, kernel arguments and
+// code stay what they were.
+template <int NJ>
+struct ChainVelK {
+  double vw[NJ], vfw[NJ];
+};
+template <int NJ>
+__device__ __forceinline__ const double* goal_rows(const ChainGoalRows& g, const ChainVelK<NJ>&) { return g.rows; }
+template <class X, class A0, class... A>
+__device__ __forceinline__ const X& pack_get(const A0& a0, const A&... a) {
+  if constexpr (std::is_same_v<A0, X>) return a0;
+  else return pack_get<X>(a...);
+}
 
 // The cost tiles that change with (x, u), the terms chain_backward4_wave forms for two joints
 // (immediate_cost_quadratization :81-109, final_cost_quadratization :134-153):
 // lx = −2qw(θ* − θ) on the joint rows, lu = 2rw·u, lfx = −2qfw(θ* − θ_N).
 // One lane per element: (b, t ≤ T, e < NX + NU), t = T the terminal row.
-// Goal: none (θ* = C.tgt) or ChainGoalRows (θ* = row b).
+// Goal: none (θ* = C.tgt) or ChainGoalRows (θ* = row b), then none or ChainVelK: the velocity
+// rows, 0 without it, are then lx = 2vw·q̇ and lfx = 2vfw·q̇_N.
 template <int NJ, int NU, class... Goal>
 __global__ __launch_bounds__(256) void chain_cost_tiles_kernel(ChainCostK<NJ> C, Goal... G, int B, int T,
                                                                const double* __restrict__ x,
@@ -437,8 +456,24 @@ __global__ __launch_bounds__(256) void chain_cost_tiles_kernel(ChainCostK<NJ> C,
 #pragma unroll
   for (int i = 1; i < NJ; ++i)
     if (i == j) { tgt = C.tgt[i]; qw = C.qw[i]; rw = C.rw[i]; qfw = C.qfw[i]; }
-  static_assert((std::is_same_v<Goal, ChainGoalRows> && ...) && sizeof...(Goal) <= 1, "Goal: none or ChainGoalRows");
-  if constexpr (sizeof...(Goal) == 1)
+  // (no local constants here: they would shift the instruction order of the instantiations without weights)
+  static_assert(sizeof...(Goal) == pack_count<ChainGoalRows, Goal...> + pack_count<ChainVelK<NJ>, Goal...> &&
+                    pack_count<ChainGoalRows, Goal...> <= 1 && pack_count<ChainVelK<NJ>, Goal...> <= 1,
+                "Goal: none or ChainGoalRows, then none or ChainVelK");
+  if constexpr (pack_count<ChainVelK<NJ>, Goal...> == 1) {  // a velocity element: 2vw·q̇ (2vfw·q̇ at T) where the code below stores 0.0
+    if (e >= NJ && e < NX) {
+      const ChainVelK<NJ>& W = pack_get<ChainVelK<NJ>>(G...);
+      double vw = W.vw[0], vfw = W.vfw[0];
+#pragma unroll
+      for (int i = 1; i < NJ; ++i)
+        if (i == e - NJ) { vw = W.vw[i]; vfw = W.vfw[i]; }
+      const double xe = x[((size_t)b * (T + 1) + t) * NX + e];
+      if (t == T) lfx[(size_t)b * NX + e] = 2.0 * vfw * xe;
+      else lx[((size_t)b * T + t) * NX + e] = 2.0 * vw * xe;
+      return;
+    }
+  }
+  if constexpr (pack_count<ChainGoalRows, Goal...> == 1)
     if (e < NJ) tgt = goal_rows(G...)[(size_t)b * NJ + e];
   if (e < NX) {
     const double xe = x[((size_t)b * (T + 1) + t) * NX + e];
@@ -454,8 +489,9 @@ __global__ __launch_bounds__(256) void chain_cost_tiles_kernel(ChainCostK<NJ> C,
 // on neither the state nor the step, so they are written when the handle is created and
 // when its cost mode changes (a task mode: q = qf = 0, r = 1, and lfxx rewritten by every
 // backward). One lane per (b, t ≤ T, element of the larger tile).
-template <int NJ, int NU>
-__global__ __launch_bounds__(256) void chain_cost_hessians_kernel(ChainCostK<NJ> C, int B, int T,
+// Vel: none, or ChainVelK — the velocity diagonals, 0 without it, are then 2vw and 2vfw.
+template <int NJ, int NU, class... Vel>
+__global__ __launch_bounds__(256) void chain_cost_hessians_kernel(ChainCostK<NJ> C, Vel... W, int B, int T,
                                                                   double* __restrict__ lxx,
                                                                   double* __restrict__ luu,
                                                                   double* __restrict__ lfxx) {
@@ -474,7 +510,20 @@ __global__ __launch_bounds__(256) void chain_cost_hessians_kernel(ChainCostK<NJ>
 #pragma unroll
   for (int i = 0; i < NU; ++i)
     if (i == ru) rw = C.rw[i];
-  if (t == T) {
+  static_assert((std::is_same_v<Vel, ChainVelK<NJ>> && ...) && sizeof...(Vel) <= 1, "Vel: none or ChainVelK");
+  if constexpr (sizeof...(Vel) == 1) {  // the weight of row r, joint or velocity
+    const ChainVelK<NJ>& V = pack_get<ChainVelK<NJ>>(W...);
+#pragma unroll
+    for (int i = 0; i < NJ; ++i)
+      if (NJ + i == r) { qw = V.vw[i]; qfw = V.vfw[i]; }
+    if (t == T) {
+      lfxx[(size_t)b * NX * NX + e] = r == c ? 2.0 * qfw : 0.0;
+    } else {
+      const size_t s = (size_t)b * T + t;
+      lxx[s * NX * NX + e] = r == c ? 2.0 * qw : 0.0;
+      if (e < NU * NU) luu[s * NU * NU + e] = ru == cu ? 2.0 * rw : 0.0;
+    }
+  } else if (t == T) {
     lfxx[(size_t)b * NX * NX + e] = (r == c && r < NJ) ? 2.0 * qfw : 0.0;
   } else {
     const size_t s = (size_t)b * T + t;
@@ -611,7 +660,10 @@ __device__ void chain_task_quad_fk(const ChainK<double, NJ>& P, const ChainTaskK
 //  * ilqr_chain_final_cost_quadratize (xstride = NX), any output null; in the joint mode
 //    (joint = 1) the handle's joint-space final cost Σ qfwᵢ(θ*ᵢ − θᵢ)² instead.
 // Goal: none, or ChainGoalRows — the goal of state s is row s (NJ doubles with joint = 1,
-// 3 otherwise; the caller has n ≤ the rows it holds).
+// 3 otherwise; the caller has n ≤ the rows it holds) — then none or ChainVelK: both uses add
+// Σ vfwᵢ q̇ᵢ² to the cost, 2vfwᵢq̇ᵢ as the velocity rows of the gradient and 2vfwᵢ on the
+// velocity diagonal of the Hessian (still exactly symmetric, the rest of those rows and
+// columns exactly 0).
 template <int NJ, class... Goal>
 __global__ __launch_bounds__(64) void chain_task_quad_kernel(ChainK<double, NJ> P, ChainTaskK C, Goal... G, int joint,
                                                              int n, const double* __restrict__ x, size_t xstride,
@@ -626,8 +678,8 @@ __global__ __launch_bounds__(64) void chain_task_quad_kernel(ChainK<double, NJ> 
   double q[NJ], c, g[NJ], H[NJ][NJ];
 #pragma unroll
   for (int i = 0; i < NJ; ++i) q[i] = xb[i];
-  static_assert((std::is_same_v<Goal, ChainGoalRows> && ...) && sizeof...(Goal) <= 1, "Goal: none or ChainGoalRows");
-  constexpr bool ROWS = sizeof...(Goal) == 1;
+  constexpr bool ROWS = pack_count<ChainGoalRows, Goal...> == 1, VEL = pack_count<ChainVelK<NJ>, Goal...> == 1;
+  static_assert(sizeof...(Goal) == (ROWS ? 1 : 0) + (VEL ? 1 : 0), "Goal: none or ChainGoalRows, then none or ChainVelK");
   if (joint) {
     c = 0.0;
 #pragma unroll
@@ -647,6 +699,35 @@ __global__ __launch_bounds__(64) void chain_task_quad_kernel(ChainK<double, NJ> 
     chain_task_quad_fk<NJ>(P, Cb, q, c, g, H);
   } else {
     chain_task_quad_fk<NJ>(P, C, q, c, g, H);
+  }
+  if constexpr (VEL) {  // … + Σ vfwᵢ q̇ᵢ²: the velocity rows of ∇ℓ_f and the velocity diagonal of ∇²ℓ_f
+    const ChainVelK<NJ>& W = pack_get<ChainVelK<NJ>>(G...);
+    double qd[NJ];
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) {
+      qd[i] = xb[NJ + i];
+      c = fma(W.vfw[i] * qd[i], qd[i], c);
+    }
+    if (cost) cost[b] = c;
+    if (grad) {
+      double* go = grad + (size_t)b * NX;
+#pragma unroll
+      for (int i = 0; i < NJ; ++i) {
+        go[i] = g[i];
+        go[NJ + i] = 2.0 * W.vfw[i] * qd[i];
+      }
+    }
+    if (hess) {
+      double* ho = hess + (size_t)b * NX * NX;
+#pragma unroll
+      for (int i = 0; i < NX; ++i)
+#pragma unroll
+        for (int j = 0; j < NX; ++j) {
+          const int lo = i < j ? i : j, hi = i < j ? j : i;
+          ho[i * NX + j] = hi < NJ ? H[lo][hi] : (lo == hi ? 2.0 * W.vfw[lo - NJ] : 0.0);
+        }
+    }
+    return;
   }
   if (cost) cost[b] = c;
   if (grad) {
@@ -675,10 +756,16 @@ struct ChainPath {
   const double* rows;
   double w;
 };
-template <class X, class... A>
-constexpr int pack_count = (0 + ... + (std::is_same_v<A, X> ? 1 : 0));
 __device__ __forceinline__ const ChainPath& path_of(const ChainGoalRows&, const ChainPath& p) { return p; }
 __device__ __forceinline__ const double* goal_rows(const ChainGoalRows& g, const ChainPath&) { return g.rows; }
+template <int NJ>
+__device__ __forceinline__ const ChainPath& path_of(const ChainGoalRows&, const ChainPath& p, const ChainVelK<NJ>&) {
+  return p;
+}
+template <int NJ>
+__device__ __forceinline__ const double* goal_rows(const ChainGoalRows& g, const ChainPath&, const ChainVelK<NJ>&) {
+  return g.rows;
+}
 
 // The per-step tiles of the path cost, one lane per (b, t < T): the quadratization of
 // w · Σₖ (πₖ(q) − rows[b, t, k])² at x[b, t] (chain_task_quad_fk on a ChainTaskK whose target
@@ -686,9 +773,11 @@ __device__ __forceinline__ const double* goal_rows(const ChainGoalRows& g, const
 // chain_cost_tiles_kernel, which runs before, wrote the velocity rows (0) and lu = 2u — and
 // the whole lxx[b, t] tile: i ≤ j computed and mirrored, so exactly symmetric, velocity rows
 // and columns exactly 0. Trajectories whose status is not OK are skipped like that kernel's.
-template <int NJ>
-__global__ __launch_bounds__(64) void chain_path_tiles_kernel(ChainK<double, NJ> P, ChainTaskK C, ChainPath path, int B,
-                                                              int T, const double* __restrict__ x,
+// Vel: none, or ChainVelK — the velocity diagonal of lxx[b, t] is then 2vw (the velocity rows
+// of lx stay chain_cost_tiles_kernel's).
+template <int NJ, class... Vel>
+__global__ __launch_bounds__(64) void chain_path_tiles_kernel(ChainK<double, NJ> P, ChainTaskK C, ChainPath path, Vel... W,
+                                                              int B, int T, const double* __restrict__ x,
                                                               const int32_t* __restrict__ status,
                                                               double* __restrict__ lx, double* __restrict__ lxx) {
   constexpr int NX = 2 * NJ;
@@ -710,12 +799,16 @@ __global__ __launch_bounds__(64) void chain_path_tiles_kernel(ChainK<double, NJ>
 #pragma unroll
   for (int i = 0; i < NJ; ++i) go[i] = g[i];
   double* ho = lxx + bt * NX * NX;
+  static_assert((std::is_same_v<Vel, ChainVelK<NJ>> && ...) && sizeof...(Vel) <= 1, "Vel: none or ChainVelK");
 #pragma unroll
   for (int i = 0; i < NX; ++i)
 #pragma unroll
     for (int j = 0; j < NX; ++j) {
       const int lo = i < j ? i : j, hi = i < j ? j : i;
-      ho[i * NX + j] = hi < NJ ? H[lo][hi] : 0.0;
+      if constexpr (sizeof...(Vel) == 1)
+        ho[i * NX + j] = hi < NJ ? H[lo][hi] : (lo == hi ? 2.0 * pack_get<ChainVelK<NJ>>(W...).vw[lo - NJ] : 0.0);
+      else
+        ho[i * NX + j] = hi < NJ ? H[lo][hi] : 0.0;
     }
 }
 
@@ -730,6 +823,7 @@ __global__ __launch_bounds__(64) void chain_path_tiles_kernel(ChainK<double, NJ>
 //    stage of 32 × that many doubles (64, 96, 128, 160) per group;
 //  * x̄_t and ū_t are stored by lanes 0..NX − 1 and NX..NX + NU − 1 (one coalesced store each).
 constexpr int CH32_LANES = 32;
+constexpr int CH32_WG = 64;  // two trajectories per workgroup (one wave)
 template <int NJ, int NU>
 struct ChainStage {
   static constexpr int N_IN = NU * 2 * NJ + 2 * NJ + NJ + 2 * NU;  // a step's record
@@ -744,7 +838,7 @@ static_assert(ChainStage<7, 7>::WORDS == 5 && ChainStage<7, 7>::SIZE == 160, "se
 // instantiations keep their instruction streams.
 // ROWS: the goal of trajectory b is row b of `goal` (NJ doubles, θ*; 3 with TASK, final_target)
 // in place of P.tgt / C.t, likewise a compile-time choice. The row rides in the stage's unused
-// tail, which every lane count leaves (12, 21, 20 and 27 words for 4..7 joints): the lanes
+// tail, which every lane count leaves (12, 21, 26 and 27 words for 4..7 joints): the lanes
 // whose words fall past the record re-read K's first word at every step anyway, so with ROWS
 // the first NG of those words read the row instead (stride 0) and the hand-off delivers it
 // to the group at stage[N_IN ..) — no register beyond what the shared-goal code holds, which
@@ -755,6 +849,12 @@ static_assert(ChainStage<7, 7>::WORDS == 5 && ChainStage<7, 7>::SIZE == 160, "se
 // as the terminal cost. Step t's row rides in the tail too, three words behind the goal row
 // at stage[N_IN + NG ..) with stride 3, prefetched one step ahead with the record. The
 // kinematics sit before the RK4 step, so their temporaries are dead at its stages.
+// Velocity weights (ChainVelK last in Goal, any mode): every step adds fma(vwᵢ·e, e, lk) in
+// joint order after the mode's terms, the terminal cost fma(vfwᵢ·x̄[NJ + i], x̄[NJ + i], lf). With
+// TASK e is the raw x̄[NJ + i]; in the joint mode it is x̄[NJ + i] − xtw·x_traj[NJ + i], and the
+// NJ velocity words of x_traj ride in the tail as well, behind the goal row at
+// stage[N_IN + NG + NP ..) with stride NX, prefetched with the record (the record itself keeps
+// its length: N_IN and every offset stay). The weights are read from an LDS copy per group.
 template <int NJ, int NU, bool TASK = false, bool ROWS = false, class... Goal>
 __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P, double* __restrict__ stage,
                                                      int b, int T, const double* __restrict__ x,
@@ -766,8 +866,9 @@ __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P
                                                      double* du2_out, const LSParams& ls,
                                                      const ChainTaskK& C = ChainTaskK{}, const Goal&... G) {
   using V = double;
-  constexpr bool PATH = pack_count<ChainPath, Goal...> == 1;
-  static_assert(pack_count<ChainGoalRows, Goal...> == (ROWS ? 1 : 0) && sizeof...(Goal) == (ROWS ? 1 : 0) + (PATH ? 1 : 0),
+  constexpr bool PATH = pack_count<ChainPath, Goal...> == 1, VEL = pack_count<ChainVelK<NJ>, Goal...> == 1;
+  static_assert(pack_count<ChainGoalRows, Goal...> == (ROWS ? 1 : 0) &&
+                    sizeof...(Goal) == (ROWS ? 1 : 0) + (PATH ? 1 : 0) + (VEL ? 1 : 0),
                 "Goal: ChainGoalRows with ROWS, else none (the shared-goal instantiations keep their signature)");
   static_assert(!PATH || (TASK && ROWS), "Goal: ChainGoalRows, ChainPath in a task mode with a path");
   constexpr int NX = 2 * NJ, NK = NU * NX;
@@ -777,8 +878,22 @@ __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P
                 "a step's inputs in NW words per lane, x̄ and ū stored by one lane each");
   constexpr int NG = ROWS ? (TASK ? 3 : NJ) : 0, O_G = N_IN;  // the goal row in the stage's tail
   constexpr int NP = PATH ? 3 : 0, O_P = O_G + NG;  // the step's path row behind it
-  static_assert(N_IN + NG + NP <= ChainStage<NJ, NU>::SIZE, "the goal row and the path row fit the stage's unused tail");
+  constexpr int NV = VEL && !TASK ? NJ : 0, O_V = O_P + NP;  // x_traj's velocity rows behind them
+  static_assert(N_IN + NG + NP + NV <= ChainStage<NJ, NU>::SIZE,
+                "the goal row, the path row and the velocity reference fit the stage's unused tail");
   const int l32 = threadIdx.x & (CH32_LANES - 1);
+  // the velocity weights: the group's own LDS copy, read where the step's cost uses them; the
+  // cost is pinned before the RK4 stages (below), so they are dead there
+  [[maybe_unused]] const ChainVelK<NJ>* W = nullptr;
+  if constexpr (VEL) {
+    __shared__ ChainVelK<NJ> Ws[CH32_WG / CH32_LANES];
+    ChainVelK<NJ>* mine = Ws + threadIdx.x / CH32_LANES;
+    static_assert(sizeof(ChainVelK<NJ>) == 2 * NJ * sizeof(double) && 2 * NJ <= CH32_LANES, "one word per lane");
+    if (l32 < 2 * NJ)
+      reinterpret_cast<double*>(mine)[l32] = reinterpret_cast<const double*>(&pack_get<ChainVelK<NJ>>(G...))[l32];
+    wave_lds_fence();
+    W = mine;
+  }
   const V* xb0 = x + (size_t)b * (T + 1) * NX;
   const V* ub0 = u + (size_t)b * T * NU;
   const V* xt0 = (xtraj ? xtraj : x) + (size_t)b * (T + 1) * NX;
@@ -807,6 +922,16 @@ __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P
           src[k] = path_of(G...).rows + (size_t)b * (T + 1) * 3 + (e - O_P);
           str[k] = 3;
         }
+      if constexpr (NV > 0)
+        if (e >= O_V && e < O_V + NV) {
+          src[k] = xt0 + NJ + (e - O_V);
+          str[k] = NX;
+        }
+    } else if constexpr (NV > 0) {
+      if (e < O_V + NV) {
+        src[k] = xt0 + NJ + (e - O_V);
+        str[k] = NX;
+      }
     }
   }
   V alpha = V(ls.alpha0);
@@ -874,7 +999,22 @@ __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P
 #pragma unroll
         for (int a = 0; a < NU; ++a) lk = fma(P.rw[a] * ubar[a], ubar[a], lk);
       }
+      if constexpr (VEL) {  // … + Σ vwᵢ q̇ᵢ², the joint mode's q̇ against x_traj's velocity rows
+#pragma unroll
+        for (int i = 0; i < NJ; ++i) {
+          V e = xb[NJ + i];
+          if constexpr (!TASK) e = fma(-xtw, stage[O_V + i], e);
+          lk = fma(W->vw[i] * e, e, lk);
+        }
+      }
       cost += lk;
+      if constexpr (VEL) {
+        // the step's cost is complete here, before the RK4 stages: left to itself the compiler
+        // sinks the whole sum behind chain_rk4_cv32 and keeps the weights and x_traj's velocity
+        // words (4·NJ registers) live across every stage
+        asm volatile("" : "+v"(cost));
+        __builtin_amdgcn_sched_barrier(0);
+      }
       {
         V w = xb[0];
 #pragma unroll
@@ -925,6 +1065,10 @@ __device__ ChainFwdOut<double> chain_forward_group32(const ChainK<double, NJ>& P
         }
       }
     }
+    if constexpr (VEL) {
+#pragma unroll
+      for (int i = 0; i < NJ; ++i) lf = fma(W->vfw[i] * xb[NJ + i], xb[NJ + i], lf);
+    }
     cost += lf;
     out.trials = trial;
     out.cost = cost;
@@ -949,8 +1093,27 @@ __device__ __forceinline__ ChainFwdOut<double> chain_forward_group32(
   return chain_forward_group32<NJ, NU, false, true>(P, stage, b, T, x, u, xtraj, dg, Kg, prev_cost, xnew, unew, du2_out,
                                                     ls, ChainTaskK{}, G);
 }
-
-constexpr int CH32_WG = 64;  // two trajectories per workgroup (one wave)
+// … and with velocity weights, with the shared goal or a goal per trajectory
+template <int NJ, int NU, bool TASK, bool ROWS>
+__device__ __forceinline__ ChainFwdOut<double> chain_forward_group32(
+    const ChainK<double, NJ>& P, double* __restrict__ stage, int b, int T, const double* __restrict__ x,
+    const double* __restrict__ u, const double* __restrict__ xtraj, const double* __restrict__ dg,
+    const double* __restrict__ Kg, double prev_cost, double* __restrict__ xnew, double* __restrict__ unew,
+    double* du2_out, const LSParams& ls, const ChainVelK<NJ>& W) {
+  static_assert(!TASK && !ROWS, "the joint-space costs with velocity weights");
+  return chain_forward_group32<NJ, NU, false, false>(P, stage, b, T, x, u, xtraj, dg, Kg, prev_cost, xnew, unew,
+                                                     du2_out, ls, ChainTaskK{}, W);
+}
+template <int NJ, int NU, bool TASK, bool ROWS>
+__device__ __forceinline__ ChainFwdOut<double> chain_forward_group32(
+    const ChainK<double, NJ>& P, double* __restrict__ stage, int b, int T, const double* __restrict__ x,
+    const double* __restrict__ u, const double* __restrict__ xtraj, const double* __restrict__ dg,
+    const double* __restrict__ Kg, double prev_cost, double* __restrict__ xnew, double* __restrict__ unew,
+    double* du2_out, const LSParams& ls, const ChainGoalRows& G, const ChainVelK<NJ>& W) {
+  static_assert(!TASK && ROWS, "the joint-space costs of a handle with a goal per trajectory and velocity weights");
+  return chain_forward_group32<NJ, NU, false, true>(P, stage, b, T, x, u, xtraj, dg, Kg, prev_cost, xnew, unew, du2_out,
+                                                    ls, ChainTaskK{}, G, W);
+}
 
 // The two forward kernels. TaskK is empty (the joint-space cost) or ChainTaskK (a task mode:
 // the TASK instantiation of the group, the task cost's constants one more kernel argument),
@@ -961,7 +1124,8 @@ constexpr int CH32_WG = 64;  // two trajectories per workgroup (one wave)
 // out <NJ, NU>, <NJ, NU, ChainTaskK>, <NJ, NU, ChainGoalRows>,
 // <NJ, NU, ChainTaskK, ChainGoalRows> or <NJ, NU, ChainTaskK, ChainGoalRows, ChainPath> (a tool
 // path: the goal rows are then the path's rows T).
-// none | ChainTaskK | ChainGoalRows | ChainTaskK, ChainGoalRows | ChainTaskK, ChainGoalRows, ChainPath
+// none | ChainTaskK | ChainGoalRows | ChainTaskK, ChainGoalRows | ChainTaskK, ChainGoalRows, ChainPath,
+// each followed by none or ChainVelK<NJ> (velocity weights: always the last of the pack)
 template <class... A>
 struct CostPack : std::false_type {};
 template <>
@@ -974,13 +1138,24 @@ template <>
 struct CostPack<ChainTaskK, ChainGoalRows> : std::true_type {};
 template <>
 struct CostPack<ChainTaskK, ChainGoalRows, ChainPath> : std::true_type {};
+// … each followed by none or ChainVelK (velocity weights)
+template <int NJ>
+struct CostPack<ChainVelK<NJ>> : std::true_type {};
+template <int NJ>
+struct CostPack<ChainTaskK, ChainVelK<NJ>> : std::true_type {};
+template <int NJ>
+struct CostPack<ChainGoalRows, ChainVelK<NJ>> : std::true_type {};
+template <int NJ>
+struct CostPack<ChainTaskK, ChainGoalRows, ChainVelK<NJ>> : std::true_type {};
+template <int NJ>
+struct CostPack<ChainTaskK, ChainGoalRows, ChainPath, ChainVelK<NJ>> : std::true_type {};
 template <int NJ, int NU, class... TaskK>
 __global__ __launch_bounds__(CH32_WG) void chain_forward32_kernel(
     ChainK<double, NJ> P, TaskK... C, int B, int T, const double* __restrict__ x, const double* __restrict__ u,
     const double* __restrict__ xtraj, const double* __restrict__ d, const double* __restrict__ K,
     const double* __restrict__ prev_cost, double* __restrict__ xnew, double* __restrict__ unew,
     double* __restrict__ new_cost, int32_t* __restrict__ trials, int32_t* __restrict__ status, LSParams ls) {
-  static_assert(CostPack<TaskK...>::value, "TaskK: none or ChainTaskK, then none or ChainGoalRows, then none or ChainPath");
+  static_assert(CostPack<TaskK...>::value, "TaskK: none or ChainTaskK, then none or ChainGoalRows, then none or ChainPath, then none or ChainVelK");
   static_assert(kernarg_bytes<ChainK<double, NJ>, TaskK..., int, int, const double*, const double*, const double*,
                               const double*, const double*, const double*, double*, double*, double*, int32_t*,
                               int32_t*, LSParams>() <= HIP_KERNARG_LIMIT,
@@ -1009,7 +1184,7 @@ __global__ __launch_bounds__(CH32_WG) void chain_iter_forward32_kernel(ChainK<do
                                                                      ChainIter<double> a,
                                                                      const int32_t* __restrict__ bstatus,
                                                                      LSParams ls) {
-  static_assert(CostPack<TaskK...>::value, "TaskK: none or ChainTaskK, then none or ChainGoalRows, then none or ChainPath");
+  static_assert(CostPack<TaskK...>::value, "TaskK: none or ChainTaskK, then none or ChainGoalRows, then none or ChainPath, then none or ChainVelK");
   static_assert(kernarg_bytes<ChainK<double, NJ>, TaskK..., int, int, ChainIter<double>, const int32_t*,
                               LSParams>() <= HIP_KERNARG_LIMIT,
                 "the chain constants by value: the argument block within HIP's limit");
@@ -1066,8 +1241,23 @@ struct ChainTilesOps {
   // ChainPath while a tool path applies (those kernels only; `rows` is then its rows T). Each
   // launch names its pack from these arguments' types, so a kernel is instantiated for the
   // packs its callers can reach and no other (the comment above CostPack).
+  // Last of every pack, ChainVelK while the handle has velocity weights.
   template <bool TASKK, class Fn>
   static hipError_t with_cost_pack(const ilqr_chain_handle* h, const double* rows, Fn&& fn) {
+    if (h->tiles.vel_on)
+      return with_goal_pack<TASKK>(h, rows, [&](auto... c) { return fn(c..., vel_consts(h)); });
+    return with_goal_pack<TASKK>(h, rows, fn);
+  }
+  static ilqr::ChainVelK<NJ> vel_consts(const ilqr_chain_handle* h) {
+    ilqr::ChainVelK<NJ> W{};
+    for (int i = 0; i < NJ; ++i) {
+      W.vw[i] = h->tiles.v_weight[i];
+      W.vfw[i] = h->tiles.vf_weight[i];
+    }
+    return W;
+  }
+  template <bool TASKK, class Fn>
+  static hipError_t with_goal_pack(const ilqr_chain_handle* h, const double* rows, Fn&& fn) {
     const ilqr::ChainGoalRows g{rows};
     if constexpr (TASKK)
       if (h->task_mode()) {
@@ -1084,8 +1274,12 @@ struct ChainTilesOps {
   // luu = 2I, and lfxx is rewritten by every backward)
   static hipError_t hessians(ilqr_chain_handle* h) {
     const size_t n = (size_t)h->batch * (h->T + 1) * NX * NX;
-    ilqr::chain_cost_hessians_kernel<NJ, NU><<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(
-        cost_consts(h->chain), h->batch, h->T, h->tiles.lxx, h->tiles.luu, h->tiles.lfxx);
+    if (h->tiles.vel_on)  // … and the velocity diagonals
+      ilqr::chain_cost_hessians_kernel<NJ, NU, ilqr::ChainVelK<NJ>><<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(
+          cost_consts(h->chain), vel_consts(h), h->batch, h->T, h->tiles.lxx, h->tiles.luu, h->tiles.lfxx);
+    else
+      ilqr::chain_cost_hessians_kernel<NJ, NU><<<(unsigned)((n + 255) / 256), 256, 0, h->stream>>>(
+          cost_consts(h->chain), h->batch, h->T, h->tiles.lxx, h->tiles.luu, h->tiles.lfxx);
     return hipGetLastError();
   }
   // A and B of trajectories with status OK (st null: all)
@@ -1126,8 +1320,13 @@ struct ChainTilesOps {
     // rows of lx and the lxx tiles from the steps' rows; the terminal tiles from x_N
     if (const double* p = t.path_rows(true)) {
       const size_t np = (size_t)h->batch * h->T;
-      ilqr::chain_path_tiles_kernel<NJ><<<(unsigned)((np + 63) / 64), 64, 0, h->stream>>>(
-          chain_consts<V, NJ>(h->chain), t.taskk, ilqr::ChainPath{p, t.path_weight}, h->batch, h->T, x, st, t.lx, t.lxx);
+      if (t.vel_on)
+        ilqr::chain_path_tiles_kernel<NJ, ilqr::ChainVelK<NJ>><<<(unsigned)((np + 63) / 64), 64, 0, h->stream>>>(
+            chain_consts<V, NJ>(h->chain), t.taskk, ilqr::ChainPath{p, t.path_weight}, vel_consts(h), h->batch, h->T, x,
+            st, t.lx, t.lxx);
+      else
+        ilqr::chain_path_tiles_kernel<NJ><<<(unsigned)((np + 63) / 64), 64, 0, h->stream>>>(
+            chain_consts<V, NJ>(h->chain), t.taskk, ilqr::ChainPath{p, t.path_weight}, h->batch, h->T, x, st, t.lx, t.lxx);
       if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     return quadratize(h, x + (size_t)h->T * NX, (size_t)(h->T + 1) * NX, h->batch, st, nullptr, t.lfx, t.lfxx);

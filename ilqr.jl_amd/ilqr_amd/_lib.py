@@ -183,6 +183,8 @@ SIGNATURES = {
     "ilqr_chain_set_joint_targets": (C.c_int, [P, P]),
     "ilqr_chain_set_task_targets": (C.c_int, [P, P]),
     "ilqr_chain_set_task_path": (C.c_int, [P, P, C.c_double]),
+    "ilqr_chain_set_velocity_weights": (C.c_int, [P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "ilqr_chain_get_velocity_weights": (C.c_int32, [P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "ilqr_chain_get_target_mode": (C.c_int32, [P]),
     "ilqr_chain_sync": (C.c_int, [P]),
     "ilqr_chain_dynamics": (C.c_int, [P, P, P, P, C.c_int]),
@@ -234,18 +236,22 @@ def load(path: str = LIB_PATH) -> C.CDLL:
 
 
 class IlqrError(RuntimeError):
-    def __init__(self, status: int, where: str):
+    def __init__(self, status: int, where: str, detail: str = ""):
         lib = load()
         msg = lib.ilqr_status_string(status).decode()
         extra = (lib.ilqr_last_error().decode() or lib.ilqr_chain_last_error().decode()
                  or lib.ilqr_floating_last_error().decode())
-        super().__init__(f"{where}: {msg}" + (f" ({extra})" if extra and status == ERR_HIP else ""))
+        super().__init__(f"{where}: {msg}" + (f" ({extra})" if extra and status == ERR_HIP else "")
+                         + (f" ({detail})" if detail else ""))
         self.status = status
 
 
-def check(status: int, where: str, allow=()) -> int:
+def check(status: int, where: str, allow=(), last_error=None) -> int:
+    """Raise IlqrError unless status is OK or allowed. last_error: the family's last-error
+    function (e.g. lib.ilqr_chain_last_error); its sentence is added to an ERR_UNSUPPORTED."""
     if status != OK and status not in allow:
-        raise IlqrError(status, where)
+        detail = last_error().decode() if last_error is not None and status == ERR_UNSUPPORTED else ""
+        raise IlqrError(status, where, detail)
     return status
 
 

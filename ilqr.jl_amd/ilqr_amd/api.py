@@ -113,6 +113,8 @@ def _chain_solver(xb, ub, dynamicsf, immediate_cost, final_cost, dtype):
     if fc is not None:
         try:
             s.set_simple_costs(fc.body, fc.point, fc.final_target, fc.weight, fc.euclidean)
+            if p.v_weight is not None:   # the simple-cost closures state no velocity term: solve what they state
+                s.set_velocity_weights(None, None)
         except Exception:
             s.close()
             raise

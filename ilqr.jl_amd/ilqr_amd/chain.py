@@ -55,7 +55,12 @@ def load_robot(name: str) -> Chain:
 
 @dataclass
 class ChainProblem:
-    """A chain plus the joint-space quadratic costs of the reference's RBD example."""
+    """A chain plus the joint-space quadratic costs of the reference's RBD example.
+    v_weight / vf_weight (optional, scalars or n_joints values): joint-velocity weights,
+    ℓ += Σ v_weightᵢ q̇ᵢ² and ℓ_f += Σ vf_weightᵢ q̇ᵢ² (ChainSolver.set_velocity_weights; four to
+    seven joints, fp64). They belong to the problem's joint-space cost (ChainCost, ChainFinalCost):
+    ilqr_amd.fit with cost_functions' simple costs on this problem solves those closures' cost,
+    without them. None, the default, for both: the reference's cost."""
     chain: Chain
     nu: int
     dt: float = RBD_DT
@@ -63,6 +68,8 @@ class ChainProblem:
     q_weight: np.ndarray = None
     r_weight: np.ndarray = None
     qf_weight: np.ndarray = None
+    v_weight: np.ndarray = None
+    vf_weight: np.ndarray = None
 
     def __post_init__(self):
         n = self.chain.n
@@ -74,6 +81,8 @@ class ChainProblem:
         self.q_weight = vec(self.q_weight, 1.0)
         self.r_weight = vec(self.r_weight, 1.0)
         self.qf_weight = vec(self.qf_weight, 1.0)
+        if self.v_weight is not None or self.vf_weight is not None:
+            self.v_weight, self.vf_weight = vec(self.v_weight, 0.0), vec(self.vf_weight, 0.0)
 
     @property
     def n_joints(self):
@@ -278,6 +287,12 @@ class ChainSolver:
         # the iteration kernels of this shape in the solver's dtype (4 to 7 joints: fp64 only)
         self.iterates = bool(self.lib.ilqr_chain_supported_dtype(
             self.nj, self.nu, _lib.F32 if dtype == torch.float32 else _lib.F64))
+        if problem.v_weight is not None:   # the problem's velocity weights (the library refuses 2 joints, fp32)
+            try:
+                self.set_velocity_weights(problem.v_weight, problem.vf_weight)
+            except Exception:
+                self.close()
+                raise
 
     def set_dynamics(self, mode: str):
         """The iteration kernels' dynamics evaluator (2-joint chains): "auto" (the closed
@@ -365,6 +380,35 @@ class ChainSolver:
             _req(path, torch.float64, (self.batch, self.T + 1, 3), "path")
         self._bind()   # the rows are copied, and the cleared mode's tiles enqueued, on the handle's stream
         _lib.check(self.lib.ilqr_chain_set_task_path(self.h, _ptr(path), float(weight)), "ilqr_chain_set_task_path")
+
+    def _weights(self, w, name):
+        """A scalar or n_joints values as the C array of a weight vector; None stays None."""
+        if w is None:
+            return None
+        a = np.asarray(w, float)
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != self.nj):
+            raise ValueError(f"{name}: a scalar or {self.nj} values, got shape {a.shape}")
+        return (C.c_double * self.nj)(*[float(v) for v in np.broadcast_to(a, (self.nj,))])
+
+    def set_velocity_weights(self, v_weight, vf_weight):
+        """Joint-velocity weights (ilqr_chain_set_velocity_weights; four to seven joints, fp64):
+        scalars or n_joints values, None for zeros. While set, every cost mode (joint, both task
+        readings, a tool path) adds Σ v_weightᵢ q̇ᵢ² to each step's cost and Σ vf_weightᵢ q̇ᵢ² at
+        T to the final cost, q̇ᵢ = x[n_joints + i]; in the joint mode the running term is measured
+        on x̄ − x_traj like the position term. (None, None) clears them. They survive changes of
+        cost mode, goals and path, and own no device memory."""
+        v, vf = self._weights(v_weight, "v_weight"), self._weights(vf_weight, "vf_weight")
+        self._bind()   # the Hessian tiles are enqueued on the handle's stream
+        _lib.check(self.lib.ilqr_chain_set_velocity_weights(self.h, v, vf), "ilqr_chain_set_velocity_weights",
+                   last_error=self.lib.ilqr_chain_last_error)   # a refusal (2 joints, fp32) with the library's sentence
+
+    @property
+    def velocity_weights(self):
+        """(v_weight, vf_weight) as arrays of n_joints values, or None when not set."""
+        v, vf = (C.c_double * self.nj)(), (C.c_double * self.nj)()
+        if int(self.lib.ilqr_chain_get_velocity_weights(self.h, v, vf)) != 1:
+            return None
+        return np.array(v[:]), np.array(vf[:])
 
     @property
     def target_mode(self) -> frozenset:
@@ -533,7 +577,8 @@ class ChainDynamics:
 
 
 class ChainCost:
-    """immediate_cost(x, u) = Σ q_weightᵢ(θ*ᵢ − θᵢ)² + Σ r_weightₖ uₖ²."""
+    """immediate_cost(x, u) = Σ q_weightᵢ(θ*ᵢ − θᵢ)² + Σ r_weightₖ uₖ² (+ Σ v_weightᵢ q̇ᵢ² of a
+    problem with velocity weights)."""
 
     def __init__(self, problem: ChainProblem):
         self.problem = problem
@@ -541,11 +586,16 @@ class ChainCost:
     def __call__(self, x, u):
         p = self.problem
         e = p.target - np.asarray(x[: p.n_joints], float)
-        return float(np.sum(p.q_weight * e * e) + np.sum(p.r_weight[: p.nu] * np.asarray(u, float) ** 2))
+        c = float(np.sum(p.q_weight * e * e) + np.sum(p.r_weight[: p.nu] * np.asarray(u, float) ** 2))
+        if p.v_weight is not None:
+            qd = np.asarray(x[p.n_joints: 2 * p.n_joints], float)
+            c += float(np.sum(p.v_weight * qd * qd))
+        return c
 
 
 class ChainFinalCost:
-    """final_cost(x) = Σ qf_weightᵢ(θ*ᵢ − θᵢ)²."""
+    """final_cost(x) = Σ qf_weightᵢ(θ*ᵢ − θᵢ)² (+ Σ vf_weightᵢ q̇ᵢ² of a problem with velocity
+    weights)."""
 
     def __init__(self, problem: ChainProblem):
         self.problem = problem
@@ -553,7 +603,11 @@ class ChainFinalCost:
     def __call__(self, x):
         p = self.problem
         e = p.target - np.asarray(x[: p.n_joints], float)
-        return float(np.sum(p.qf_weight * e * e))
+        c = float(np.sum(p.qf_weight * e * e))
+        if p.vf_weight is not None:
+            qd = np.asarray(x[p.n_joints: 2 * p.n_joints], float)
+            c += float(np.sum(p.vf_weight * qd * qd))
+        return c
 
 
 def chain_closures(problem: ChainProblem):

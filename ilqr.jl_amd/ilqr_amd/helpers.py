@@ -179,6 +179,11 @@ def immediate_cost_quadratization(x, u, immediate_cost):
         qv[:n] = -2.0 * w * e
         Q = torch.zeros((nx, nx), dtype=torch.float64, device=dev)
         Q[:n, :n] = torch.diag(2.0 * w)
+        if p.v_weight is not None:   # … + Σ v_weightᵢ q̇ᵢ²
+            vw, qd = _t(p.v_weight, dev), xt[n: 2 * n]
+            q = q + (vw * qd * qd).sum()
+            qv[n: 2 * n] = 2.0 * vw * qd
+            Q[n: 2 * n, n: 2 * n] = torch.diag(2.0 * vw)
         return _ret(as_torch, q, qv, 2.0 * rw * ut, Q, P, torch.diag(2.0 * rw))
     if isinstance(immediate_cost, SimpleImmediateCost):  # cost_functions.jl:45-51: Σ uᵢ²
         Z = torch.zeros((nx, nx), dtype=torch.float64, device=dev)
@@ -224,7 +229,13 @@ def final_cost_quadratization(x, final_cost):
         qv[:n] = -2.0 * w * e
         Q = torch.zeros((nx, nx), dtype=torch.float64, device=dev)
         Q[:n, :n] = torch.diag(2.0 * w)
-        return _ret(as_torch, (w * e * e).sum(), qv, Q)
+        c = (w * e * e).sum()
+        if p.vf_weight is not None:   # … + Σ vf_weightᵢ q̇ᵢ²
+            vw, qd = _t(p.vf_weight, dev), xt[n: 2 * n]
+            c = c + (vw * qd * qd).sum()
+            qv[n: 2 * n] = 2.0 * vw * qd
+            Q[n: 2 * n, n: 2 * n] = torch.diag(2.0 * vw)
+        return _ret(as_torch, c, qv, Q)
     f = final_cost
     if isinstance(final_cost, SimpleFinalCost):
         f = _simple_final_cost_torch(final_cost)

@@ -1023,6 +1023,30 @@ function set_task_path!(s::ChainSolver, path::Union{Nothing,Array{Float64,3}}, w
     return s
 end
 
+"""set_velocity_weights!(s, v, vf): joint-velocity weights, `n_joints` values each, a scalar for
+all joints, or `nothing` for zeros. While set, every cost mode adds Σ vᵢ q̇ᵢ² to a step's cost and
+Σ vfᵢ q̇ᵢ² at the horizon to the final cost; `nothing, nothing` clears them."""
+function set_velocity_weights!(s::ChainSolver, v, vf)
+    what = "ilqr_chain_set_velocity_weights"
+    vec(w) = w === nothing ? nothing : (w isa Real ? fill(Float64(w), s.nj) : Vector{Float64}(w))
+    a, b = vec(v), vec(vf)
+    for w in (a, b)
+        w === nothing || length(w) == s.nj ||
+            throw(DimensionMismatch("$what: expected $(s.nj) values, got $(length(w))"))
+    end
+    p(w) = w === nothing ? Ptr{Float64}(C_NULL) : pointer(w)
+    GC.@preserve a b check(ccall((:ilqr_chain_set_velocity_weights, libilqr), Cint,
+                                 (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), s.ch, p(a), p(b)), what)
+    return s
+end
+
+"""velocity_weights(s): `(v, vf)` as vectors, or `nothing` when no weights are set."""
+function velocity_weights(s::ChainSolver)
+    v, vf = zeros(s.nj), zeros(s.nj)
+    on = ccall((:ilqr_chain_get_velocity_weights, libilqr), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), s.ch, v, vf)
+    return on == 1 ? (v, vf) : nothing
+end
+
 target_mode(s::ChainSolver) = ccall((:ilqr_chain_get_target_mode, libilqr), Int32, (Ptr{Cvoid},), s.ch)
 
 const CHAIN_CACHE = Dict{Tuple{Chain,Int,Int,DataType,Int32,Int32,Union{Nothing,SimpleCosts}},ChainSolver}()

@@ -516,8 +516,10 @@ ilqr_status ilqr_chain_set_task_costs(ilqr_chain_handle* h, int32_t mode, int32_
 /* final_cost_quadratization (backward_pass.jl:134-153) of the handle's cost in effect at
  * n states: cost (n), grad (n, nx), hess (n, nx, nx); any of the three may be NULL.
  * x (n, nx), fp64, device memory; enqueued on the handle's stream. ILQR_F64 handles of
- * 4 to 7 joints (ILQR_ERR_UNSUPPORTED elsewhere). hess is exactly symmetric and its velocity
- * rows and columns are exactly 0. */
+ * 4 to 7 joints (ILQR_ERR_UNSUPPORTED elsewhere). hess is exactly symmetric. Without velocity
+ * weights its velocity rows and columns are exactly 0; with them
+ * (ilqr_chain_set_velocity_weights) the velocity block is exactly diag(2·vf_weight), cost and
+ * grad carry the term, and everything else in those rows and columns stays exactly 0. */
 ilqr_status ilqr_chain_final_cost_quadratize(ilqr_chain_handle* h, const void* x, int n,
                                              void* cost, void* grad, void* hess);
 /* the cost mode in effect, −1 for a NULL handle */
@@ -583,6 +585,32 @@ ilqr_status ilqr_chain_set_task_targets(ilqr_chain_handle* h, const double* targ
  * ILQR_ERR_UNSUPPORTED with a sentence in ilqr_chain_last_error; a non-finite path_weight
  * with a path → ILQR_ERR_BAD_ARG, the handle's state unchanged. */
 ilqr_status ilqr_chain_set_task_path(ilqr_chain_handle* h, const double* path, double path_weight);
+/* Joint-velocity weights, for handles that iterate on the tiles path (4 to 7 joints, fp64):
+ * "reach the goal and stop there". While they are set every cost mode gains
+ *   ℓ_t(x, u) += Σᵢ v_weightᵢ · q̇ᵢ²      t < T,   q̇ᵢ = x[n_joints + i]
+ *   ℓ_f(x_T)  += Σᵢ vf_weightᵢ · (q̇ᵢ at T)²
+ * in ILQR_CHAIN_COST_JOINT, in both task readings and with a tool path, with or without goals
+ * per trajectory, under every linearisation, through backward, forward, iterate, fit, fit_ex
+ * and ilqr_chain_final_cost_quadratize. In the joint mode the forward pass measures the
+ * running term on x̄ − x_traj like the position term (x_traj == NULL: zeros); the task modes
+ * keep ignoring x_traj; ℓ_f and every derivative are on the raw state. The derivatives are
+ * lx[n+i] = 2·v_weightᵢ·q̇ᵢ, lxx[n+i, n+i] = 2·v_weightᵢ and the same with vf_weight at T; no
+ * position–velocity cross term.
+ * v_weight, vf_weight: HOST pointers to n_joints doubles each, shared by the whole batch like
+ * q_weight. Either may be NULL (zeros for that vector); both NULL clears the weights. They
+ * are kept as plain values in the handle and reach the kernels by value: the call allocates
+ * nothing, ever. They survive every change of cost mode, goal rows and path. Setting,
+ * replacing and clearing enqueue the Hessian tiles of the cost in effect on the handle's
+ * stream. A handle that never had weights launches the kernels it launched before this entry
+ * point existed. Negative finite weights are accepted, as negative q_weights are.
+ * Returns, before any device call and with the handle unchanged: NULL handle →
+ * ILQR_ERR_BAD_ARG; a handle that does not iterate on the tiles path (any 2-joint chain, 4 to
+ * 7 joints in ILQR_F32) → ILQR_ERR_UNSUPPORTED with a sentence in ilqr_chain_last_error; any
+ * non-finite weight → ILQR_ERR_BAD_ARG. */
+ilqr_status ilqr_chain_set_velocity_weights(ilqr_chain_handle* h, const double* v_weight, const double* vf_weight);
+/* 1 when velocity weights are set, 0 when not, −1 for a NULL handle. Fills whichever of the
+ * two outputs (n_joints doubles, host) is not NULL; zeros when nothing is set. */
+int32_t ilqr_chain_get_velocity_weights(const ilqr_chain_handle* h, double* v_weight, double* vf_weight);
 /* bit 0: joint targets per trajectory, bit 1: task targets per trajectory, bit 2: a tool
  * path; −1 for a NULL handle */
 int32_t ilqr_chain_get_target_mode(const ilqr_chain_handle* h);

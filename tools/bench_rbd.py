@@ -72,12 +72,14 @@ def cpu_baseline(pr, x, u, budget_s):
 
 def measure(lin="fd", B=2048, T=100, nu=1, dtype="f32", steps=100, warmup=100, device=0,
             dynamics="auto", cpu_budget=None, base=None, problem=None, simple_cost=False, robot=None,
-            fit=True, targets="shared"):
+            fit=True, targets="shared", velocity_weights=None):
     """Config 5's fit-iteration rate and per-kernel roofline for one linearisation (one
     dict; bench.py's secondary_configs calls this after its headline, outside the
     headline's timed region). targets="per-trajectory" (4 to 7 joints): every trajectory
     its own goal, the problem's plus an offset from default_rng(TARGET_SEED + b)
-    (ilqr_chain_set_joint_targets, or _set_task_targets with simple_cost)."""
+    (ilqr_chain_set_joint_targets, or _set_task_targets with simple_cost).
+    velocity_weights=(v, vf) (4 to 7 joints): joint-velocity weights on every joint
+    (ilqr_chain_set_velocity_weights)."""
     dt = torch.float32 if dtype == "f32" else torch.float64
     dev = torch.device("cuda", device)
     # problem: another chain (the coupled 2-joint test chain: q-dependent M and bias, which
@@ -94,6 +96,8 @@ def measure(lin="fd", B=2048, T=100, nu=1, dtype="f32", steps=100, warmup=100, d
         rows = np.stack([goal + np.random.default_rng(TARGET_SEED + b).uniform(-TARGET_SPREAD, TARGET_SPREAD,
                                                                                goal.size) for b in range(B)])
         (s.set_task_targets if simple_cost else s.set_joint_targets)(rows)
+    if velocity_weights is not None:
+        s.set_velocity_weights(*velocity_weights)
     u = torch.zeros((B, T, pr.nu), dtype=dt, device=dev)
     x = s.rollout(torch.from_numpy(x0).to(dev, dt), u)
     xn, un = torch.empty_like(x), torch.empty_like(u)
@@ -179,6 +183,7 @@ def measure(lin="fd", B=2048, T=100, nu=1, dtype="f32", steps=100, warmup=100, d
                                    "BASELINE config 5 (RBD_2_link_example, fixed base)"),
                       "batch": B, "T": T, "linearization": lin, "dynamics": s.dynamics_mode,
                       "cost_mode": s.cost_mode, "targets": targets,
+                      "velocity_weights": None if velocity_weights is None else list(velocity_weights),
                       "closed_form_check": s.closed_form_error},
            "traj_iters_per_s": B * 1000.0 / ms,
            "mean_line_search_trials": float(trials.double().mean().item()), "all_ok": ok,
@@ -247,6 +252,9 @@ def main():
     ap.add_argument("--targets", default="shared", choices=["shared", "per-trajectory"],
                     help="per-trajectory (6dof_arm, coupled): a goal per trajectory, the problem's plus a seeded "
                          "per-trajectory offset (ilqr_chain_set_joint_targets / _set_task_targets)")
+    ap.add_argument("--velocity-weights", default=None, metavar="V,VF",
+                    help="joint-velocity weights on every joint, running and terminal "
+                         "(ilqr_chain_set_velocity_weights; --robot 6dof_arm or coupled)")
     ap.add_argument("--no-fit", action="store_true",
                     help="skip the end-to-end ChainSolver.fit timing (90 synchronous fits)")
     args = ap.parse_args()
@@ -268,13 +276,20 @@ def main():
         ap.error("--simple-cost goes with --robot 6dof_arm or coupled")
     if args.targets != "shared" and args.robot == "2dof_arm":
         ap.error("--targets per-trajectory goes with --robot 6dof_arm or coupled (the tiles path)")
+    vel = None
+    if args.velocity_weights is not None:
+        if args.robot == "2dof_arm":
+            ap.error("--velocity-weights goes with --robot 6dof_arm or coupled (the tiles path)")
+        vel = tuple(float(v) for v in args.velocity_weights.split(","))
+        if len(vel) != 2:
+            ap.error("--velocity-weights V,VF")
     for lin in args.lin.split(","):
         res = measure(lin, args.batch, args.T, args.nu, args.dtype, args.steps, args.warmup,
                       dynamics=args.dynamics,
                       cpu_budget=None if args.no_cpu or args.simple_cost or lin == "analytic" else args.cpu_budget,
                       base=base,
                       problem=problem, simple_cost=args.simple_cost, robot=robot,
-                      fit=not args.no_fit, targets=args.targets)
+                      fit=not args.no_fit, targets=args.targets, velocity_weights=vel)
         base = res["cpu_baseline"] or base
         print(json.dumps(res), flush=True)
 
